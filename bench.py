@@ -6,7 +6,10 @@ GATsSPG matcher (12 layers, dual softmax, mutual NN; conf_matrix materialised) -
 correspondence selection -> RANSAC-EPnP -> cm/deg error vs GT.  Inputs are resident in HBM
 before the timed region; nothing is cached across steps.
 
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W]      (the headline figure only)
+    python bench.py --full     (also the per-kernel profile pass, the dominant kernel's roofline
+                                from device stamps, and the CPU baseline)
+    python bench.py --dump-outputs DIR   (the last timed step's outputs as DIR/<name>.npy)
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N  (one rank/GPU)
     python bench.py --e2e      (extra measurement: each step starts from 512x512 images --
                                 SuperPoint on the GPU produces the 1k query keypoints)
@@ -234,6 +237,24 @@ def summarize_pose(res, world, B, F, steps):
                       else "the last step's frames (one batch replayed every step)"}
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, last, result_rows):
+    """--dump-outputs: the last timed step's outputs (`last`: name -> device tensor) and the
+    timed region's gathered per-frame result rows as <out_dir>/<name>.npy.  fp32 stays fp32;
+    fp64 and the integer outputs (indices, counts, flags: exact in a double) go out as fp64."""
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {"result_rows": result_rows, **last}
+    total = 0
+    for name, t in arrays.items():
+        a = t.detach().cpu().numpy()
+        a = np.ascontiguousarray(a, np.float32 if a.dtype == np.float32 else np.float64)
+        total += a.nbytes
+        assert total <= DUMP_LIMIT_BYTES, f"--dump-outputs: more than {DUMP_LIMIT_BYTES} bytes"
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -248,7 +269,18 @@ def main():
     ap.add_argument("--n1", type=int, default=1024)
     ap.add_argument("--n3", type=int, default=4096)
     ap.add_argument("--leaf", type=int, default=8)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also everything beyond the headline figure: the per-kernel profile "
+                         "pass (kernel_ms_per_step), the dominant kernel's device stamps in the "
+                         "timed region (roofline; with --e2e the detector's conv figures) and "
+                         "the CPU baseline.  A plain run sets up, warms up, times the steps and "
+                         "prints value / ms_per_step / pose / frame_roofline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed (the "
+                         "frame's matches and scores, pose, inliers, cm/deg errors) and the "
+                         "timed region's gathered result rows as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true",
+                    help="with --full: skip the CPU baseline")
     ap.add_argument("--serial", action="store_true",
                     help="one stream: step k+1 starts after step k's pose stage (default: the "
                          "pose stage of step k overlaps the matcher of step k+1 on 2 streams)")
@@ -388,18 +420,21 @@ def main():
     pipe.enqueue()
     torch.cuda.synchronize()
 
-    # per-kernel profile pass (all kinds, HIP events, eager) to find the dominant kernel
+    # --full: per-kernel profile pass (all kinds, HIP events, eager) to find the dominant kernel
     names = profile_kinds(lib)
-    kinds, ms = run_profiled(lib, pipe, 3, (1 << len(names)) - 1, 4096)
-    per_kind = {}
-    for k, t in zip(kinds, ms):
-        per_kind.setdefault(names[k], []).append(float(t))
-    total = {k: sum(v) / 3.0 for k, v in per_kind.items()}
-    mean_launch = {k: sum(v) / len(v) for k, v in per_kind.items()}
-    # the dominant kernel is timed by device stamps, which the token GEMMs record
-    dominant = max((k for k in total if kernel_work(k, B, n1, n3, L, cached) and k in STAMPED),
-                   key=lambda k: total[k])
-    dom_id = names.index(dominant)
+    total, mean_launch, dominant, dom_id = {}, {}, None, None
+    if args.full:
+        kinds, ms = run_profiled(lib, pipe, 3, (1 << len(names)) - 1, 4096)
+        per_kind = {}
+        for k, t in zip(kinds, ms):
+            per_kind.setdefault(names[k], []).append(float(t))
+        total = {k: sum(v) / 3.0 for k, v in per_kind.items()}
+        mean_launch = {k: sum(v) / len(v) for k, v in per_kind.items()}
+        # the dominant kernel is timed by device stamps, which the token GEMMs record
+        dominant = max((k for k in total
+                        if kernel_work(k, B, n1, n3, L, cached) and k in STAMPED),
+                       key=lambda k: total[k])
+        dom_id = names.index(dominant)
 
     # Timed region: K steps; every step runs every kernel of the frame path.  With graphs
     # (default) the matcher stage and the pose stage are each one HIP-graph replay (captured
@@ -409,9 +444,9 @@ def main():
     # stamping must be on while the graphs are captured (the accumulator address is a kernel
     # argument); begin_device again below re-zeroes the same accumulators
     sp_id = names.index("sp_conv")
-    stamp_mask = (1 << dom_id) | ((1 << sp_id) if args.e2e else 0)
-    if args.no_stamps:   # diagnostic: what device stamping costs the timed region
-        stamp_mask = 0
+    # a plain run records no stamps: they feed only --full's roofline / detector figures
+    stamps_on = args.full and not args.no_stamps   # (--no-stamps: what stamping costs)
+    stamp_mask = ((1 << dom_id) | ((1 << sp_id) if args.e2e else 0)) if stamps_on else 0
     _lib.check(lib.onepose_profile_begin_device(stamp_mask), "profile_begin_device")
     # staged inputs (FramePipeline.prime_inputs): each pose stage ends with the input stage of
     # the step that next uses its slot, so the matcher's launch chain starts at its first layer
@@ -486,6 +521,24 @@ def main():
                           slot.cmd.double(), slot.n_inliers[:, None].double(),
                           slot.status[:, None].double(), frame_ids], 1)
 
+    def last_step_outputs():
+        """What the last timed step computed: its slot's matcher outputs and, from the bank
+        entry's result rows (without a bank: the slot's), its pose stage's."""
+        if not overlap or args.diag_steps:
+            g = 0
+        else:   # staged steps continue the bank across run_steps calls
+            g = (pipe._next_step if staged else args.steps) - 1
+        o = pipe.slots[g % len(pipe.slots)]
+        if bank is not None and overlap:
+            r = {k: v[g % F] for k, v in pipe.bank_results.items()}
+        else:
+            r = {k: getattr(o, k) for k in ("pose", "R_err", "t_err", "cmd", "n_inliers", "status")}
+        # rows past the frame's correspondence count are not written by the pose stage
+        live = torch.arange(n1, device=dev)[None, :] < o.counts[:, None]
+        return {"matches0": o.matches0, "matches1": o.matches1, "mscores0": o.mscores0,
+                "mscores1": o.mscores1, "n_correspondences": o.counts,
+                "inlier_mask": o.inlier_mask * live, **r}
+
     n_rows = world * B * (F or 1)   # gathered result rows (global frames)
 
     # first replay of each graph (upload) and the first use of every torch kernel the timed
@@ -522,14 +575,17 @@ def main():
     launches, tot_ms = np.zeros(nk, np.int64), np.zeros(nk, np.float64)
     _lib.check(lib.onepose_profile_end_device(launches.ctypes.data, tot_ms.ctypes.data, nk),
                "profile_end_device")
-    alone_ms = float(mean_launch[dominant])
-    n_dom = int(launches[dom_id])
-    if args.no_stamps:
-        n_dom, dom_ms = 0, alone_ms
-    else:
-        assert n_dom > 0 and tot_ms[dom_id] > 0, "dominant-kernel timing missing"
-        dom_ms = float(tot_ms[dom_id] / n_dom)
+    if args.full:
+        alone_ms = float(mean_launch[dominant])
+        n_dom = int(launches[dom_id])
+        if args.no_stamps:
+            n_dom, dom_ms = 0, alone_ms
+        else:
+            assert n_dom > 0 and tot_ms[dom_id] > 0, "dominant-kernel timing missing"
+            dom_ms = float(tot_ms[dom_id] / n_dom)
     elapsed = D.max_over_ranks(elapsed, dev)   # the slowest rank's clock
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last_step_outputs(), result)
 
     stage_ms = None
     if marks:   # matcher / pose stage GPU times over the timed region (diagnostic)
@@ -569,7 +625,7 @@ def main():
     res = result.cpu().numpy()
     frames_total = world * B * args.steps
     det = None
-    if args.e2e:
+    if args.e2e and stamps_on:
         S = args.image_size
         conv_ms = float(tot_ms[sp_id])
         conv_flop = superpoint_conv_flops(S, S) * B * args.steps
@@ -584,42 +640,47 @@ def main():
                                             / FP32_MFMA_PEAK_TFLOPS, 4),
                "timing": "sum of SuperPoint MFMA-conv launch durations (device clock)"}
     value = frames_total / elapsed
-    work, unit, bound = kernel_work(dominant, B, n1, n3, L, cached)
-    achieved = work / (dom_ms * 1e-3) / 1e12
-    bf_dom = args.precision == "bf16" and dominant in ("qkv_gemm", "mlp1_gemm", "mlp2_gemm")
-    peak = BF16_MFMA_PEAK_TFLOPS if bf_dom else FP32_MFMA_PEAK_TFLOPS
-    traffic, traffic_src = None, None
-    if (B, n1, n3, L) == (1, 1024, 4096, 8) and args.precision == "fp32":
-        traffic, traffic_src = pmc_traffic(dominant)
-    elif (B, n1, n3, L) == (1, 2048, 8192, 8) and args.precision == "bf16":
-        traffic, traffic_src = pmc_traffic(dominant + ("_bf16" if bf_dom else ""), "pmc_c5")
-    roof = {"bound": "mfma", "achieved": round(achieved, 2), "peak": peak,
-            "unit": "TFLOP/s", "frac": round(achieved / peak, 4),
-            "traffic": traffic, "traffic_unit": "HBM bytes per launch (PMC)",
-            "traffic_source": traffic_src, "kernel": dominant,
-            "avg_launch_us": round(dom_ms * 1e3, 2),
-            "launches_timed": n_dom, "flop_per_launch": work,
-            "timing": "device clock, first workgroup start to last workgroup end",
-            # context: the same kernel when nothing else runs (serial profile pass before the
-            # timed region, HIP events); inside the timed region a launch shares the chip with
-            # the other match stream's kernels
-            "alone": {"avg_launch_us": round(alone_ms * 1e3, 2),
-                      "frac": round(work / (alone_ms * 1e-3) / 1e12 / peak, 4),
-                      "timing": "serial profile pass (3 steps), HIP events per launch"}}
+    roof = None
+    if args.full:
+        work, unit, bound = kernel_work(dominant, B, n1, n3, L, cached)
+        achieved = work / (dom_ms * 1e-3) / 1e12
+        bf_dom = args.precision == "bf16" and dominant in ("qkv_gemm", "mlp1_gemm", "mlp2_gemm")
+        peak = BF16_MFMA_PEAK_TFLOPS if bf_dom else FP32_MFMA_PEAK_TFLOPS
+        traffic, traffic_src = None, None
+        if (B, n1, n3, L) == (1, 1024, 4096, 8) and args.precision == "fp32":
+            traffic, traffic_src = pmc_traffic(dominant)
+        elif (B, n1, n3, L) == (1, 2048, 8192, 8) and args.precision == "bf16":
+            traffic, traffic_src = pmc_traffic(dominant + ("_bf16" if bf_dom else ""), "pmc_c5")
+        roof = {"bound": "mfma", "achieved": round(achieved, 2), "peak": peak,
+                "unit": "TFLOP/s", "frac": round(achieved / peak, 4),
+                "traffic": traffic, "traffic_unit": "HBM bytes per launch (PMC)",
+                "traffic_source": traffic_src, "kernel": dominant,
+                "avg_launch_us": round(dom_ms * 1e3, 2),
+                "launches_timed": n_dom, "flop_per_launch": work,
+                "timing": "device clock, first workgroup start to last workgroup end",
+                # context: the same kernel when nothing else runs (serial profile pass before
+                # the timed region, HIP events); inside the timed region a launch shares the
+                # chip with the other match stream's kernels
+                "alone": {"avg_launch_us": round(alone_ms * 1e3, 2),
+                          "frac": round(work / (alone_ms * 1e-3) / 1e12 / peak, 4),
+                          "timing": "serial profile pass (3 steps), HIP events per launch"}}
 
-    # SURVEY.md §8d "fraction = F * frames/s / peak" for the whole frame's contractions
-    ff = frame_flops(n1, n3, L, cached, B)
-    formula = ("F_dep - 688128 n3 (object prefix and cross-attention 1's 3D half cached)"
-               if cross_cached(cached, B) else "F_dep (object prefix cached)" if cached else "F")
-    fx = executed_mfma_flops(n1, n3, cached)
-    frame_roof = {"basis": "algorithmic (SURVEY.md section 8d)", "flop_per_frame": ff,
-                  "formula": formula, "achieved_tflops": round(ff * value / 1e12, 2),
-                  "peak": peak, "frac": round(ff * value / 1e12 / peak, 4),
-                  "executed": {"mfma_flop_per_frame": fx,
-                               "achieved_tflops": round(fx * value / 1e12, 2),
-                               "frac": round(fx * value / 1e12 / peak, 4),
-                               "note": "MFMA FLOPs the kernels execute (the Mf fold removes the "
-                                       "merge conv and the attention apply)"}}
+    frame_roof = None
+    if args.full:
+        # SURVEY.md §8d "fraction = F * frames/s / peak" for the whole frame's contractions
+        ff = frame_flops(n1, n3, L, cached, B)
+        formula = ("F_dep - 688128 n3 (object prefix and cross-attention 1's 3D half cached)"
+                   if cross_cached(cached, B)
+                   else "F_dep (object prefix cached)" if cached else "F")
+        fx = executed_mfma_flops(n1, n3, cached)
+        frame_roof = {"basis": "algorithmic (SURVEY.md section 8d)", "flop_per_frame": ff,
+                      "formula": formula, "achieved_tflops": round(ff * value / 1e12, 2),
+                      "peak": peak, "frac": round(ff * value / 1e12 / peak, 4),
+                      "executed": {"mfma_flop_per_frame": fx,
+                                   "achieved_tflops": round(fx * value / 1e12, 2),
+                                   "frac": round(fx * value / 1e12 / peak, 4),
+                                   "note": "MFMA FLOPs the kernels execute (the Mf fold removes the "
+                                           "merge conv and the attention apply)"}}
 
     # the gathered rows are the global frames (one object's sequence sharded over ranks); with
     # a bank, step j's global batch is frames [j world B, (j + 1) world B), and a row's weight is
@@ -691,8 +752,8 @@ def main():
                        "parallelism": f"frame-dp{world} (one object; global batch of "
                                       f"{n_global} frames sharded contiguously over ranks)"},
             "pose": pose_summary,
-            "roofline": roof,
-            "frame_roofline": frame_roof,
+            "full": args.full,
+            **({"roofline": roof, "frame_roofline": frame_roof} if args.full else {}),
             **({"detector": det} if det else {}),
             "host_enqueue_ms_per_step": round(host_enqueue / args.steps * 1e3, 4),
             "library": {"path": os.path.relpath(_lib.LIB_PATH, REPO),
@@ -700,11 +761,13 @@ def main():
             **({"diagnostic": "pose stage skipped (--diag-no-pose): not the metric"}
                if args.diag_no_pose else {}),
             **({"stage_ms": stage_ms} if stage_ms else {}),
-            "kernel_ms_per_step": {k: round(v, 4) for k, v in sorted(total.items(),
-                                                                     key=lambda kv: -kv[1])},
+            **({"kernel_ms_per_step": {k: round(v, 4) for k, v in sorted(total.items(),
+                                                                         key=lambda kv: -kv[1])}}
+               if args.full else {}),
             **({"diag_ms_per_step": diag} if diag else {}),
+            **({"outputs_dumped": args.dump_outputs} if args.dump_outputs else {}),
         }
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(sd, data, frames, obj,
                                                detector_image=images[0] if args.e2e else None)
         print(json.dumps(out))

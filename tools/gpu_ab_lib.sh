@@ -8,7 +8,7 @@ mkdir -p $O
 L=onepose_amd/libonepose_hip.so
 run() {   # name, lib, args
   cp onepose_amd/libonepose_hip_$2.so $L
-  timeout -k 10 200 python bench.py --no-cpu-baseline $3 > $O/$1.json 2> $O/$1.err || exit $?
+  timeout -k 10 200 python bench.py --full --no-cpu-baseline $3 > $O/$1.json 2> $O/$1.err || exit $?
   python -c "import json; d=json.loads(open('$O/$1.json').read().strip().splitlines()[-1]); k=d['kernel_ms_per_step']; print('$1', d['value'], {x: k[x] for x in ('mlp1_gemm','qkv_gemm','mlp2_gemm','score_gemm')})"
 }
 for i in 1 2; do

@@ -13,7 +13,7 @@ fi
 for r in $(seq 1 ${ROUNDS:-2}); do
   for v in ${VARIANTS:-$A $B}; do
     for s in ${STEPLIST:-300 20}; do
-      ONEPOSE_LIB=$PWD/tools/ab/lib_$v.so timeout -k 10 200 python bench.py --steps $s --warmup 5 \
+      ONEPOSE_LIB=$PWD/tools/ab/lib_$v.so timeout -k 10 200 python bench.py --full --steps $s --warmup 5 \
         --no-cpu-baseline ${BENCH_ARGS:-} > $O/${v}_s${s}_$r.json 2> $O/${v}_s${s}_$r.err || exit $?
       python -c "import json; d=json.loads(open('$O/${v}_s${s}_$r.json').read().strip().splitlines()[-1]); k=d['kernel_ms_per_step']; print('$v s$s r$r', d['value'], d['ms_per_step'], {x: k.get(x) for x in ('mlp1_gemm','qkv_gemm','kv_reduce')})"
     done

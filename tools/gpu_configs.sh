@@ -3,12 +3,13 @@
 # config-4 per-GPU shard (1024 x 2500, 32 frames per GPU), fp32; config 5 shape in bf16.
 set -u
 export TMPDIR=/tmp
-mkdir -p gpurun_out/configs
+O=${OUT:-bench_out}/configs
+mkdir -p $O
 run() {
   local name=$1; shift
-  timeout -k 10 300 python bench.py "$@" > gpurun_out/configs/$name.json 2> gpurun_out/configs/$name.err
+  timeout -k 10 300 python bench.py --full "$@" > $O/$name.json 2> $O/$name.err
   local rc=$?
-  echo "$name rc=$rc"; tail -c 600 gpurun_out/configs/$name.json; echo
+  echo "$name rc=$rc"; tail -c 600 $O/$name.json; echo
   return $rc
 }
 run config3 --n3 16384 --batch 32 --steps 10 --warmup 2 --no-cpu-baseline &&

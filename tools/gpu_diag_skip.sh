@@ -8,7 +8,7 @@ export TMPDIR=/tmp
 O=gpurun_out/${OUT:-diag}
 mkdir -p $O
 for v in ${VARIANTS:-base kvf l2smx confmut trgat mlp1 qkv mlp2 score base}; do
-  ONEPOSE_LIB=$PWD/tools/ab/lib_$v.so timeout -k 10 200 python bench.py --steps ${STEPS:-300} --warmup 5 \
+  ONEPOSE_LIB=$PWD/tools/ab/lib_$v.so timeout -k 10 200 python bench.py --full --steps ${STEPS:-300} --warmup 5 \
     --no-cpu-baseline --diag-no-pose ${BENCH_ARGS:-} > $O/$v.json 2> $O/$v.err || exit $?
   python -c "import json; d=json.loads(open('$O/$v.json').read().strip().splitlines()[-1]); print('$v', d['value'], d['ms_per_step'])"
 done

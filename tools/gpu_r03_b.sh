@@ -10,7 +10,7 @@ for cfg in c2 c5; do
   mkdir -p $O/pmc_$cfg
   for c in FETCH_SIZE WRITE_SIZE; do
     timeout -s KILL 240 rocprofv3 --pmc $c --kernel-trace --output-format csv -d $O/pmc_$cfg/$c -o run -- \
-      python3 bench.py --steps 10 --warmup 3 --no-cpu-baseline --serial --eager $ARGS \
+      python3 bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --serial --eager $ARGS \
       > $O/pmc_$cfg/bench_$c.json 2> $O/pmc_$cfg/bench_$c.err || exit $?
     echo "pmc $cfg $c ok"
   done
@@ -19,7 +19,7 @@ for cfg in c2 c5; do
   timeout -s KILL 240 rocprofv3 --pmc SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY \
     SQ_ACTIVE_INST_ANY SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE \
     --kernel-trace --output-format csv -d $O/sq_$cfg/raw -o run -- \
-    python3 bench.py --steps 10 --warmup 3 --no-cpu-baseline --serial --eager $ARGS \
+    python3 bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --serial --eager $ARGS \
     > $O/sq_$cfg/bench.json 2> $O/sq_$cfg/bench.err || exit $?
   python3 tools/pmc_summary.py --sq $O/sq_$cfg/raw > $O/sq_$cfg/sq_summary.json || exit $?
   echo "sq $cfg ok"

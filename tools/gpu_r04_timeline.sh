@@ -6,7 +6,7 @@ export TMPDIR=/tmp
 O=gpurun_out/${OUT:-timeline}
 mkdir -p $O/prof
 timeout -s KILL 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof -o run -- \
-  python3 bench.py --steps 100 --warmup 5 --no-cpu-baseline > $O/bench.json 2> $O/bench.err || exit $?
+  python3 bench.py --full --steps 100 --warmup 5 --no-cpu-baseline > $O/bench.json 2> $O/bench.err || exit $?
 f=$(find $O/prof -name "*kernel_trace.csv" | head -1)
 python tools/gaps.py $f 40 > $O/gaps.txt 2>&1; cat $O/gaps.txt
 python tools/timeline.py $f 40 > $O/timeline.txt 2>&1; cat $O/timeline.txt

@@ -8,7 +8,7 @@ mkdir -p gpurun_out/sq
 timeout -s KILL 240 rocprofv3 --pmc SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY \
   SQ_ACTIVE_INST_ANY SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE \
   --kernel-trace --output-format csv -d gpurun_out/sq/raw -o run -- \
-  python3 bench.py --steps ${STEPS:-10} --warmup 3 --no-cpu-baseline --serial --eager ${BENCH_ARGS:-} \
+  python3 bench.py --full --steps ${STEPS:-10} --warmup 3 --no-cpu-baseline --serial --eager ${BENCH_ARGS:-} \
   > gpurun_out/sq/bench.json 2> gpurun_out/sq/bench.err
 rc=$?
 echo "sq rc=$rc"

@@ -18,7 +18,7 @@ if [ -z "${SKIP_TESTS:-}" ]; then
   tail -1 $O/gpu_tests.log
 fi
 line() {   # tag, args
-  timeout -k 10 200 python bench.py --no-cpu-baseline $2 > $O/$1.json 2> $O/$1.err || exit $?
+  timeout -k 10 200 python bench.py --full --no-cpu-baseline $2 > $O/$1.json 2> $O/$1.err || exit $?
   python -c "import json; d=json.loads(open('$O/$1.json').read().strip().splitlines()[-1]); k=d['kernel_ms_per_step']; print('$1', d['value'], d['ms_per_step'], {x: k.get(x) for x in ('conf','score_gemm','mutual','kv_reduce','gat')})"
 }
 line n300_1 "--steps 300 --warmup 5"

@@ -7,7 +7,7 @@ export TMPDIR=/tmp
 O=gpurun_out/${OUT:-r05cumask}
 mkdir -p $O
 line() {   # tag, args
-  timeout -k 10 200 python bench.py --no-cpu-baseline $2 > $O/$1.json 2> $O/$1.err || { tail -5 $O/$1.err; exit 1; }
+  timeout -k 10 200 python bench.py --full --no-cpu-baseline $2 > $O/$1.json 2> $O/$1.err || { tail -5 $O/$1.err; exit 1; }
   python -c "import json; d=json.loads(open('$O/$1.json').read().strip().splitlines()[-1]); print('$1', d['value'])"
 }
 line m8_smoke "--steps 20 --warmup 5 --diag-cu-mask 8"

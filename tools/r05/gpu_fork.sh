@@ -19,7 +19,7 @@ if [ -z "${SKIP_TESTS:-}" ]; then
   tail -1 $O/gpu_tests.log
 fi
 line() {   # tag, lib, args
-  ONEPOSE_LIB=$2 timeout -k 10 200 python bench.py --no-cpu-baseline $3 > $O/$1.json 2> $O/$1.err || exit $?
+  ONEPOSE_LIB=$2 timeout -k 10 200 python bench.py --full --no-cpu-baseline $3 > $O/$1.json 2> $O/$1.err || exit $?
   python -c "import json; d=json.loads(open('$O/$1.json').read().strip().splitlines()[-1]); k=d['kernel_ms_per_step']; print('$1', d['value'], d['ms_per_step'], {x: k.get(x) for x in ('qkv_gemm','gat','kv_reduce')})"
 }
 for r in 1 2; do
@@ -34,7 +34,7 @@ line c5_A $A "--steps 100 --warmup 5 --precision bf16 --desc-dtype fp16 --n1 204
 line c5_B $B "--steps 100 --warmup 5 --precision bf16 --desc-dtype fp16 --n1 2048 --n3 8192"
 mkdir -p $O/prof
 timeout -s KILL 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof -o run -- \
-  python3 bench.py --steps 100 --warmup 5 --no-cpu-baseline > $O/prof/bench.json 2> $O/prof/bench.err || exit $?
+  python3 bench.py --full --steps 100 --warmup 5 --no-cpu-baseline > $O/prof/bench.json 2> $O/prof/bench.err || exit $?
 f=$(find $O/prof -name "*kernel_trace.csv" | head -1)
 python tools/timeline.py $f 40 > $O/timeline.txt 2>&1; cat $O/timeline.txt
 gzip $f

@@ -5,7 +5,7 @@ export TMPDIR=/tmp
 O=gpurun_out/${OUT:-r05streams}
 mkdir -p $O
 line() {   # tag, args
-  timeout -k 10 200 python bench.py --no-cpu-baseline $2 > $O/$1.json 2> $O/$1.err || exit $?
+  timeout -k 10 200 python bench.py --full --no-cpu-baseline $2 > $O/$1.json 2> $O/$1.err || exit $?
   python -c "import json; d=json.loads(open('$O/$1.json').read().strip().splitlines()[-1]); print('$1', d['value'])"
 }
 for r in 1 2; do

@@ -4,7 +4,7 @@ set -o pipefail
 O=gpurun_out/r06c34
 mkdir -p $O
 one() {   # name, args
-  timeout -k 10 300 python bench.py --no-cpu-baseline $2 > $O/$1.json 2> $O/$1.err || exit 1
+  timeout -k 10 300 python bench.py --full --no-cpu-baseline $2 > $O/$1.json 2> $O/$1.err || exit 1
   python -c "import json; d=json.loads(open('$O/$1.json').read().strip().splitlines()[-1]); print('$1', d['value'], d['ms_per_step'], d['pose']['cmd5'])"
 }
 C3="--n3 16384 --batch 32 --steps 10 --warmup 2"

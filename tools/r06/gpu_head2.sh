@@ -4,7 +4,7 @@ set -o pipefail
 O=gpurun_out/r06head2
 mkdir -p $O
 one() {   # name, args
-  timeout -k 10 200 python bench.py --no-cpu-baseline $2 > $O/$1.json 2> $O/$1.err || exit 1
+  timeout -k 10 200 python bench.py --full --no-cpu-baseline $2 > $O/$1.json 2> $O/$1.err || exit 1
   python -c "import json; d=json.loads(open('$O/$1.json').read().strip().splitlines()[-1]); print('$1', d['value'], d['ms_per_step'], d['pose']['cmd5'])"
 }
 for i in 1 2 3 4; do

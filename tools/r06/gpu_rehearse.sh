@@ -6,7 +6,7 @@ O=gpurun_out/r06reh
 mkdir -p $O
 reh() {   # name, env, args
   env ONEPOSE_REHEARSE_ONE_GPU=1 $2 timeout -k 10 200 python -m torch.distributed.run --nnodes=1 \
-    --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29533 bench.py --gpus 2 --steps 20 \
+    --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29533 bench.py --full --gpus 2 --steps 20 \
     --warmup 5 --no-cpu-baseline $3 > $O/$1.json 2> $O/$1.err || exit 1
   python -c "import json; d=json.loads(open('$O/$1.json').read().strip().splitlines()[-1]); print('$1', d['value'], d['ms_per_step'])"
 }

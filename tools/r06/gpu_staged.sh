@@ -17,11 +17,11 @@ flags() {   # base: no staging; sN: the pose stream's part of the forward from s
 }
 for i in 1 2 3; do
   for v in $VARS; do
-    timeout -k 10 150 python bench.py --steps 20 --warmup 5 --no-cpu-baseline $(flags $v) > $O/s20_${v}_$i.json 2> $O/s20_${v}_$i.err || exit 1
+    timeout -k 10 150 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline $(flags $v) > $O/s20_${v}_$i.json 2> $O/s20_${v}_$i.err || exit 1
   done
 done
 for i in 1 2; do
   for v in $VARS; do
-    timeout -k 10 200 python bench.py --steps 300 --no-cpu-baseline $(flags $v) > $O/s300_${v}_$i.json 2> $O/s300_${v}_$i.err || exit 1
+    timeout -k 10 200 python bench.py --full --steps 300 --no-cpu-baseline $(flags $v) > $O/s300_${v}_$i.json 2> $O/s300_${v}_$i.err || exit 1
   done
 done

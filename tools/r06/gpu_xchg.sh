@@ -10,8 +10,8 @@ for v in base SLOW RMW; do
 done
 for i in 1 2; do
   for v in base SLOW RMW; do
-    ONEPOSE_LIB=$PWD/tools/ab/lib_$v.so timeout -k 10 200 python bench.py --steps 300 --no-cpu-baseline > $O/s300_${v}_$i.json 2>/dev/null || exit 1
-    ONEPOSE_LIB=$PWD/tools/ab/lib_$v.so timeout -k 10 200 python bench.py --steps 300 --precision fp32_split --no-cpu-baseline > $O/split_${v}_$i.json 2>/dev/null || exit 1
+    ONEPOSE_LIB=$PWD/tools/ab/lib_$v.so timeout -k 10 200 python bench.py --full --steps 300 --no-cpu-baseline > $O/s300_${v}_$i.json 2>/dev/null || exit 1
+    ONEPOSE_LIB=$PWD/tools/ab/lib_$v.so timeout -k 10 200 python bench.py --full --steps 300 --precision fp32_split --no-cpu-baseline > $O/split_${v}_$i.json 2>/dev/null || exit 1
     python -c "import json; a=json.loads(open('$O/s300_${v}_$i.json').read().strip().splitlines()[-1]); b=json.loads(open('$O/split_${v}_$i.json').read().strip().splitlines()[-1]); print('$v', a['value'], a['kernel_ms_per_step']['mlp1_gemm'], b['value'], b['kernel_ms_per_step']['mlp1_gemm'])"
   done
 done
