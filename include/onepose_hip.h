@@ -59,7 +59,8 @@ enum { ONEPOSE_DT_F32 = 0, ONEPOSE_DT_F16 = 1 };
 const char* onepose_last_error(void);
 /* ABI version, bumped on any signature change or new entry point (4: the per-precision
  * workspace and object-cache size queries; 5: the object cache's device-side header and
- * onepose_device_errors; 6: onepose_match_cached_stages). */
+ * onepose_device_errors; 6: onepose_match_cached_stages; 7:
+ * onepose_match_workspace_region). */
 int onepose_abi_version(void);
 /* (ABI 5) The library's sticky device-side error bits (ONEPOSE_DEVERR_*), set by kernels that
  * cannot return a status: *bits receives them, and `clear` != 0 resets them.  Synchronises with
@@ -300,6 +301,29 @@ int onepose_match_cached_stages(const void* packed_weights,
                                 float* mscores0, float* mscores1, float* conf,
                                 void* workspace, size_t workspace_bytes, int first_stage,
                                 int last_stage, void* stream);
+
+/* (ABI 7) Where a stage of onepose_match_cached_stages leaves its result, for a caller (a
+ * test) that runs the forward a stage at a time and reads the workspace in between.  A
+ * host-side query: no device call.  For a forward of this shape (with_conf: conf != NULL) and
+ * precision, after the stages INPUTS..after_stage have run, `region` is
+ *   ONEPOSE_REGION_STATE2D / _STATE3D   the 2D / 3D token state, [batch][n][256] fp32 (the GNN
+ *                                       layers alternate between two buffers per side, so the
+ *                                       answer depends on after_stage);
+ *   ONEPOSE_REGION_DESC2D / _DESC3D     the projected, L2-normalised descriptors,
+ *                                       [batch][n][256] fp32 (after_stage >= ONEPOSE_STAGE_FINAL,
+ *                                       ONEPOSE_ERR_INVALID before).
+ * *where = ONEPOSE_WHERE_WORKSPACE: *bytes bytes at *offset bytes into the workspace.
+ * *where = ONEPOSE_WHERE_OBJECT_CACHE (the 3D state up to ONEPOSE_STAGE_LAYER0 + 1: GAT 0 and the
+ * 3D half of self-attention 1 are the object's): the first n3*256 floats of the object cache,
+ * "the 3D state entering layer 2", [n3][256] shared by the batch; *offset = 0.
+ * The score matrix needs no query: after ONEPOSE_STAGE_SCORE with a conf buffer S is in conf,
+ * after ONEPOSE_STAGE_WINNERS conf holds conf_matrix. */
+enum { ONEPOSE_REGION_STATE2D = 0, ONEPOSE_REGION_STATE3D = 1, ONEPOSE_REGION_DESC2D = 2,
+       ONEPOSE_REGION_DESC3D = 3 };
+enum { ONEPOSE_WHERE_WORKSPACE = 0, ONEPOSE_WHERE_OBJECT_CACHE = 1 };
+int onepose_match_workspace_region(int batch, int n1, int n3, int num_leaf, int with_conf,
+                                   int precision, int region, int after_stage, int* where,
+                                   size_t* offset, size_t* bytes);
 
 /* ------------------------------------------------------------------------------------ *
  * N3-sharded single frame (SURVEY.md §8e optional / §8f rank 4): one frame's 3D points split

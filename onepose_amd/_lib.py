@@ -20,9 +20,11 @@ c_void_p, c_char_p = ctypes.c_void_p, ctypes.c_char_p
 
 # onepose_allgather_fn: int (*)(size_t bytes_per_rank, void* stream, void* user)
 ALLGATHER_FN = ctypes.CFUNCTYPE(c_int, c_size_t, c_void_p, c_void_p)
-ABI_VERSION = 6
+ABI_VERSION = 7
 DEVERR_STALE_CACHE = 1   # ONEPOSE_DEVERR_STALE_CACHE
 STAGE_INPUTS, STAGE_LAYER0, STAGE_FINAL, STAGE_SCORE, STAGE_WINNERS = 0, 1, 13, 14, 15  # ABI 6
+REGION_STATE2D, REGION_STATE3D, REGION_DESC2D, REGION_DESC3D = 0, 1, 2, 3   # ABI 7
+WHERE_WORKSPACE, WHERE_OBJECT_CACHE = 0, 1   # ONEPOSE_WHERE_*
 OBJ_GAT_TABLES = 1   # ONEPOSE_OBJ_GAT_TABLES
 DT_F32, DT_F16 = 0, 1   # ONEPOSE_DT_*
 
@@ -55,6 +57,10 @@ PROTOTYPES = {
                                             c_float, c_float, c_int, c_int, c_void_p, c_void_p,
                                             c_void_p, c_void_p, c_void_p, c_void_p, c_size_t,
                                             c_int, c_int, c_void_p]),
+    "onepose_match_workspace_region": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, c_int,
+                                               c_int, ctypes.POINTER(c_int),
+                                               ctypes.POINTER(c_size_t),
+                                               ctypes.POINTER(c_size_t)]),
     "onepose_match": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64,
                               c_int, c_int, c_int, c_int, c_float, c_float,
                               c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
@@ -173,6 +179,17 @@ def object_cache_bytes(lib, n3, L, flags, precision) -> int:
     if hasattr(lib, "onepose_object_cache_bytes_ex"):
         return lib.onepose_object_cache_bytes_ex(n3, L, flags, int(precision))
     return lib.onepose_object_cache_bytes(n3, L, flags)
+
+
+def workspace_region(lib, B, n1, n3, L, with_conf, precision, region, after_stage):
+    """onepose_match_workspace_region: (where, byte offset, byte count) of `region` (REGION_*)
+    after the stages up to `after_stage` of a cached forward; where is WHERE_*."""
+    where, off, nbytes = c_int(0), c_size_t(0), c_size_t(0)
+    check(lib.onepose_match_workspace_region(B, n1, n3, L, int(with_conf), int(precision),
+                                             int(region), int(after_stage), ctypes.byref(where),
+                                             ctypes.byref(off), ctypes.byref(nbytes)),
+          "match_workspace_region")
+    return int(where.value), int(off.value), int(nbytes.value)
 
 
 def check(rc: int, what: str = "") -> None:

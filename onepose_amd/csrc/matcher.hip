@@ -1551,7 +1551,7 @@ using namespace onepose;
 extern "C" {
 
 const char* onepose_last_error(void) { return g_last_error.c_str(); }
-int onepose_abi_version(void) { return 6; }
+int onepose_abi_version(void) { return 7; }
 
 int onepose_profile_begin(uint64_t kind_mask, int capacity) {
   clear_error();
@@ -2215,6 +2215,24 @@ int attention_layer(const ApW& w, const Side* sd, int nside, int B, const Plan& 
   });
 }
 
+// Which of the plan's two buffers per side (Plan::x2 / Plan::x3) holds the side's state, and
+// whether the 3D state is still the object cache's: the one bookkeeping of match_impl's layer
+// loop, also read by onepose_match_workspace_region.  A GNN layer writes the buffer the state is
+// not in (c ^ 1) and after() then flips the side; a GAT layer has no 2D half, and the layers a
+// cached forward takes from the object (GAT 0, the 3D half of self-attention 1) write no 3D state.
+struct StateSlots {
+  int c2 = 0, c3 = 0;
+  bool x3_cached;
+  explicit StateSlots(bool cached) : x3_cached(cached) {}
+  static bool from_cache(bool cached, int layer) { return cached && layer < 2; }
+  void after(int layer, bool cached) {
+    if (layer % 3 != 0) c2 ^= 1;               // 'self' / 'cross': a 2D half
+    if (from_cache(cached, layer)) return;     // the 3D side comes from the cache
+    c3 ^= 1;
+    x3_cached = false;
+  }
+};
+
 // The matcher forward on point-major leaves [*, n3*L, 256] (leaves_pm_bs elements per sample).
 // obj_cache (onepose_match_cached): the 3D side entering layer 2, [n3][256] shared by the
 // batch (onepose_object_prepare) -- GAT 0 and the 3D half of self-attention 1 are skipped.
@@ -2346,7 +2364,8 @@ int match_impl(const void* packed_weights, const void* desc2d, int64_t desc2d_bs
   // Current states: side x is read from x?r (batch stride x?bs) and written to p.x?[c? ^ 1];
   // their activation planes (bf16 modes) from x?pr (null: the object cache's state, which only
   // cached halves read)
-  int c2 = 0, c3 = 0, ap = 0, gat = 0;
+  StateSlots sl(obj_cache != nullptr);
+  int ap = 0, gat = 0;
   const float* x2r = p.x2[0];
   const float* x3r = obj_cache ? obj_cache : p.x3[0];
   int64_t x3bs = obj_cache ? 0 : (int64_t)n3 * 256;
@@ -2358,7 +2377,9 @@ int match_impl(const void* packed_weights, const void* desc2d, int64_t desc2d_bs
     // later one): the loop only tracks which buffers hold the states
     const bool run_layers = in_range(ONEPOSE_STAGE_LAYER0 + layer);
     const int kind = layer % 3;  // 0 GATs, 1 self, 2 cross
-    const bool cached3 = obj_cache && layer < 2;   // the 3D side comes from the cache
+    // the 3D side comes from the cache
+    const bool cached3 = StateSlots::from_cache(obj_cache != nullptr, layer);
+    const int c2 = sl.c2, c3 = sl.c3;   // the buffers holding the states entering this layer
     if (kind == 0) {
       if (!cached3) {
         const dim3 ggrid(ceil_div(B * n3, 4));
@@ -2383,10 +2404,10 @@ int match_impl(const void* packed_weights, const void* desc2d, int64_t desc2d_bs
           OP_LAUNCH(K_GAT, st, gat_kernel<16>, ggrid, dim3(256), 0, st, x3r, leaves,
                     leaves_bstride, gat_weights(wbase, gat), slog, p.x3[c3 ^ 1], n3, num_leaf, B,
                     yp, npl);
-        x3r = p.x3[c3 ^ 1];
         x3pr = yp;
-        c3 ^= 1;
       }
+      sl.after(layer, obj_cache != nullptr);
+      if (!sl.x3_cached) x3r = p.x3[sl.c3];
       ++gat;
       continue;
     }
@@ -2428,14 +2449,13 @@ int match_impl(const void* packed_weights, const void* desc2d, int64_t desc2d_bs
       rc = attention_layer(w, sd, 2, B, p, lcnt, st, pm, sh, tl);
     }
     if (rc != ONEPOSE_OK) return rc;
-    x2r = p.x2[c2 ^ 1];
+    sl.after(layer, obj_cache != nullptr);
+    x2r = p.x2[sl.c2];
     x2pr = sd[0].xop;
-    c2 ^= 1;
     if (!cached3) {
-      x3r = p.x3[c3 ^ 1];
+      x3r = p.x3[sl.c3];
       x3pr = sd[1].xop;
       x3bs = (int64_t)n3 * 256;
-      c3 ^= 1;
     }
   }
 
@@ -2903,6 +2923,47 @@ int onepose_match_cached_stages(const void* packed_weights, const void* desc2d, 
                     matches0, matches1, mscores0, mscores1, conf, p,
                     static_cast<hipStream_t>(stream_), precision, nullptr, object_cache,
                     object_flags, desc_dtype, &hdr, first_stage, last_stage);
+}
+
+int onepose_match_workspace_region(int batch, int n1, int n3, int num_leaf, int with_conf,
+                                   int precision, int region, int after_stage, int* where,
+                                   size_t* offset, size_t* bytes) {
+  clear_error();
+  OP_REQUIRE(where && offset && bytes, "workspace_region: null output");
+  OP_REQUIRE(batch >= 1 && n1 >= 1 && n3 >= 1 && num_leaf >= 1 && num_leaf <= 16,
+             "workspace_region: batch=%d n1=%d n3=%d num_leaf=%d", batch, n1, n3, num_leaf);
+  OP_REQUIRE(valid_precision(precision), "workspace_region: precision %d", precision);
+  OP_REQUIRE(after_stage >= ONEPOSE_STAGE_INPUTS && after_stage <= ONEPOSE_STAGE_WINNERS,
+             "workspace_region: stage %d", after_stage);
+  OP_REQUIRE(region >= ONEPOSE_REGION_STATE2D && region <= ONEPOSE_REGION_DESC3D,
+             "workspace_region: region %d", region);
+  const bool desc = region == ONEPOSE_REGION_DESC2D || region == ONEPOSE_REGION_DESC3D;
+  OP_REQUIRE(!desc || after_stage >= ONEPOSE_STAGE_FINAL,
+             "workspace_region: the final descriptors exist from ONEPOSE_STAGE_FINAL on (stage %d)",
+             after_stage);
+  // the plan of a workspace at a stand-in base address: its pointers give the offsets
+  const uintptr_t base = (uintptr_t)1 << 30;
+  const Plan p = make_plan(reinterpret_cast<void*>(base), batch, n1, n3, num_leaf, with_conf != 0,
+                           precision != ONEPOSE_PREC_FP32);
+  // the states after the GNN layers of stages INPUTS..after_stage of a cached forward
+  StateSlots sl(true);
+  for (int layer = 0; layer < kLayers && ONEPOSE_STAGE_LAYER0 + layer <= after_stage; ++layer)
+    sl.after(layer, true);
+  const bool side3 = region == ONEPOSE_REGION_STATE3D || region == ONEPOSE_REGION_DESC3D;
+  const float* at = region == ONEPOSE_REGION_STATE2D   ? p.x2[sl.c2]
+                    : region == ONEPOSE_REGION_STATE3D ? p.x3[sl.c3]
+                    : region == ONEPOSE_REGION_DESC2D  ? p.f2
+                                                       : p.f3;
+  if (region == ONEPOSE_REGION_STATE3D && sl.x3_cached) {
+    *where = ONEPOSE_WHERE_OBJECT_CACHE;   // [n3][256], one object for the whole batch
+    *offset = 0;
+    *bytes = (size_t)n3 * 256 * sizeof(float);
+    return ONEPOSE_OK;
+  }
+  *where = ONEPOSE_WHERE_WORKSPACE;
+  *offset = (size_t)(reinterpret_cast<uintptr_t>(at) - base);
+  *bytes = (size_t)batch * (side3 ? n3 : n1) * 256 * sizeof(float);
+  return ONEPOSE_OK;
 }
 
 int onepose_device_errors(int clear, unsigned* bits) {

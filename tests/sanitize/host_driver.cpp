@@ -18,7 +18,7 @@ float frand() {
 }  // namespace
 
 int main() {
-  if (onepose_abi_version() != 6) return 1;
+  if (onepose_abi_version() != 7) return 1;
   // matcher packer
   {
     const int n = onepose_matcher_num_tensors();
@@ -76,6 +76,25 @@ int main() {
       for (int r = 0; r < world; ++r) acc += onepose_match_sharded_workspace_bytes(B, n1, n3, world, r, L, 1);
     }
     acc += onepose_pnp_workspace_bytes(B, n1, 10000);
+    // where each stage leaves the states / final descriptors: inside the workspace, or the cache
+    for (int prec = 0; prec <= 2; ++prec) {
+      const size_t ws = onepose_match_workspace_bytes_ex(B, n1, n3, L, 1, prec);
+      for (int stage = ONEPOSE_STAGE_INPUTS; stage <= ONEPOSE_STAGE_WINNERS; ++stage)
+        for (int region = ONEPOSE_REGION_STATE2D; region <= ONEPOSE_REGION_DESC3D; ++region) {
+          int where = -1;
+          size_t off = 0, bytes = 0;
+          const int rc = onepose_match_workspace_region(B, n1, n3, L, 1, prec, region, stage,
+                                                        &where, &off, &bytes);
+          const bool desc = region >= ONEPOSE_REGION_DESC2D;
+          if (desc && stage < ONEPOSE_STAGE_FINAL) {
+            if (rc == ONEPOSE_OK) return 7;
+            continue;
+          }
+          if (rc != ONEPOSE_OK || bytes == 0) return 8;
+          if (where == ONEPOSE_WHERE_WORKSPACE && off + bytes > ws) return 9;
+          acc += off + bytes;
+        }
+    }
   }
   acc += onepose_superpoint_workspace_bytes(1, 512, 512) + onepose_superpoint_detect_workspace_bytes(2, 480, 640);
   std::printf("size queries ok (%zu)\n", acc);

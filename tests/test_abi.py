@@ -30,7 +30,7 @@ def test_library_exports_every_header_symbol():
     missing = [s for s in header_symbols() if not hasattr(lib, s)]
     assert not missing, missing
     assert set(header_symbols()) == set(_lib.PROTOTYPES), "ctypes prototypes out of sync"
-    assert lib.onepose_abi_version() == _lib.ABI_VERSION == 6
+    assert lib.onepose_abi_version() == _lib.ABI_VERSION == 7
 
 
 def test_object_cache_size_follows_its_flags():
@@ -250,3 +250,50 @@ def test_match_cached_stages_rejects_bad_ranges():
                                              first, last, None)
         assert rc != 0
         assert b"stages" in lib.onepose_last_error()
+
+
+@pytest.mark.parametrize("prec", [0, 2])
+@pytest.mark.parametrize("B,n1,n3,L", [(1, 65, 97, 8), (6, 200, 330, 6)])
+def test_match_workspace_region(B, n1, n3, L, prec):
+    """onepose_match_workspace_region (ABI 7), a host-side query: each side's state alternates
+    between two workspace buffers, flipping after every layer that writes it ('self' and 'cross'
+    for the 2D side; every layer from 2 on for the 3D side of a cached forward, whose state up to
+    layer 1 is the object cache's first n3*256 floats); the final descriptors exist from
+    ONEPOSE_STAGE_FINAL on; every region lies inside the workspace and none overlaps another."""
+    from onepose_amd import _lib
+    lib = _lib.load()
+    ws_bytes = _lib.workspace_bytes(lib, B, n1, n3, L, True, prec)
+
+    def q(region, stage):
+        return _lib.workspace_region(lib, B, n1, n3, L, True, prec, region, stage)
+    buf2, buf3 = q(_lib.REGION_STATE2D, _lib.STAGE_INPUTS), q(_lib.REGION_STATE3D, _lib.STAGE_LAYER0 + 2)
+    assert buf2 == (_lib.WHERE_WORKSPACE, 0, B * n1 * 1024)
+    seen2, seen3 = [buf2], [buf3]
+    flips2 = flips3 = 0
+    for i in range(12):
+        stage = _lib.STAGE_LAYER0 + i
+        r2, r3 = q(_lib.REGION_STATE2D, stage), q(_lib.REGION_STATE3D, stage)
+        flips2 += i % 3 != 0
+        assert r2[0] == _lib.WHERE_WORKSPACE and r2[2] == B * n1 * 1024
+        if r2 not in seen2:
+            seen2.append(r2)
+        assert r2 == seen2[flips2 % 2], (i, r2)
+        if i < 2:
+            assert r3 == (_lib.WHERE_OBJECT_CACHE, 0, n3 * 1024)
+            continue
+        flips3 += i > 2
+        assert r3[0] == _lib.WHERE_WORKSPACE and r3[2] == B * n3 * 1024
+        if r3 not in seen3:
+            seen3.append(r3)
+        assert r3 == seen3[flips3 % 2], (i, r3)
+    assert len(seen2) == 2 and len(seen3) == 2
+    last = [q(_lib.REGION_STATE2D, _lib.STAGE_WINNERS), q(_lib.REGION_STATE3D, _lib.STAGE_WINNERS)]
+    assert last == [seen2[0], seen3[1]]   # 8 attention layers; 10 layers from the first 3D buffer
+    descs = [q(_lib.REGION_DESC2D, _lib.STAGE_FINAL), q(_lib.REGION_DESC3D, _lib.STAGE_SCORE)]
+    spans = sorted((off, off + nb) for _, off, nb in seen2 + seen3 + descs)
+    assert all(a[1] <= b[0] for a, b in zip(spans, spans[1:])) and spans[-1][1] <= ws_bytes
+    with pytest.raises(_lib.OnePoseError, match="ONEPOSE_STAGE_FINAL"):
+        q(_lib.REGION_DESC3D, _lib.STAGE_LAYER0 + 11)
+    for bad in ((4, 0), (-1, 0), (0, 16), (0, -1)):
+        with pytest.raises(_lib.OnePoseError):
+            q(*bad)
