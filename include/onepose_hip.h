@@ -60,7 +60,7 @@ const char* onepose_last_error(void);
 /* ABI version, bumped on any signature change or new entry point (4: the per-precision
  * workspace and object-cache size queries; 5: the object cache's device-side header and
  * onepose_device_errors; 6: onepose_match_cached_stages; 7:
- * onepose_match_workspace_region). */
+ * onepose_match_workspace_region; 8: onepose_pnp_max_points). */
 int onepose_abi_version(void);
 /* (ABI 5) The library's sticky device-side error bits (ONEPOSE_DEVERR_*), set by kernels that
  * cannot return a status: *bits receives them, and `clear` != 0 resets them.  Synchronises with
@@ -400,8 +400,15 @@ int onepose_select_correspondences(const int64_t* matches0, const float* kpts2d,
  *   2 = RANSAC found no model (identity pose, no inliers);
  * Exactly 4 points follow solvePnPRansac's P3P branch: the P3P kernel (Gao) decides model / no
  * model (status 2), the pose is the EPnP refit over all four.
+ * A 5-point EPnP (every RANSAC hypothesis) has a two-dimensional null space; its basis, which
+ * an SVD leaves arbitrary, is made canonical so that a model is a function of its five points.
  * All device pointers.
+ * (ABI 8) max_points is limited by the 160 KB of LDS a workgroup can hold: the solver keeps
+ * its state and the frame's points (20 B each) there.  onepose_pnp_max_points() is the largest
+ * max_points (and the largest n1 of onepose_pose_stage) that fits, a host-side query; a larger
+ * one is refused with ONEPOSE_ERR_INVALID before anything is launched.
  * ------------------------------------------------------------------------------------ */
+int onepose_pnp_max_points(void);
 size_t onepose_pnp_workspace_bytes(int batch, int max_points, int max_iters);
 int onepose_pnp_ransac(const float* pts2d, const float* pts3d, const int* counts,
                        int max_points, const double* K, int64_t K_bstride, int batch,

@@ -20,7 +20,7 @@ c_void_p, c_char_p = ctypes.c_void_p, ctypes.c_char_p
 
 # onepose_allgather_fn: int (*)(size_t bytes_per_rank, void* stream, void* user)
 ALLGATHER_FN = ctypes.CFUNCTYPE(c_int, c_size_t, c_void_p, c_void_p)
-ABI_VERSION = 7
+ABI_VERSION = 8
 DEVERR_STALE_CACHE = 1   # ONEPOSE_DEVERR_STALE_CACHE
 STAGE_INPUTS, STAGE_LAYER0, STAGE_FINAL, STAGE_SCORE, STAGE_WINNERS = 0, 1, 13, 14, 15  # ABI 6
 REGION_STATE2D, REGION_STATE3D, REGION_DESC2D, REGION_DESC3D = 0, 1, 2, 3   # ABI 7
@@ -105,6 +105,7 @@ PROTOTYPES = {
     "onepose_select_correspondences": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int64,
                                                c_int, c_int, c_int, c_double, c_void_p, c_void_p,
                                                c_void_p, c_void_p]),
+    "onepose_pnp_max_points": (c_int, []),   # ABI 8
     "onepose_pnp_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
     "onepose_pnp_ransac": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int64, c_int,
                                    c_double, c_float, c_int, c_double, c_void_p, c_void_p,

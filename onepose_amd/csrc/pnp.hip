@@ -703,6 +703,34 @@ __device__ __forceinline__ void rodrigues_v2m(const double* r, double* R) {
   for (int i = 0; i < 9; ++i) R[i] = c * ((i % 4 == 0) ? 1.0 : 0.0) + c1 * rrt[i] + s * rx[i];
 }
 
+// Five points give M (10 x 12) an exactly two-dimensional null space, so the two eigenvectors
+// an eigensolver returns for it are an arbitrary basis of that plane (they differ between
+// eigensolvers, and between this kernel and the oracle).  Where a pose fits the five points
+// Gauss-Newton ends at the same model from any basis; where none does (a subset with an
+// outlier in it) its five fixed iterations do not.  So for n == 5 both implementations turn
+// the pair into a canonical basis of the same plane, as canon_null2 in oracle/epnp_ransac.c:
+// v0 = the plane's unit vector nearest r = the control points' z components (the depths,
+// which dominate a camera-frame solution), v1 = its normal in the plane, signed by the sum
+// of the x components.
+__device__ __forceinline__ void canon_null2(double (&a)[12], double (&b)[12]) {
+  const double al = a[2] + a[5] + a[8] + a[11], be = b[2] + b[5] + b[8] + b[11];
+  const double nrm = sqrt(al * al + be * be);
+  if (!(nrm > 1e-9)) return;
+  const double c = al / nrm, s = be / nrm;
+  double sx = 0.0;
+#pragma unroll
+  for (int k = 0; k < 12; ++k) {
+    const double x = a[k], y = b[k];
+    a[k] = c * x + s * y;
+    b[k] = c * y - s * x;
+    if (k % 3 == 0) sx += b[k];
+  }
+  if (sx < 0.0) {
+#pragma unroll
+    for (int k = 0; k < 12; ++k) b[k] = -b[k];
+  }
+}
+
 // ---------------------------------------------------------------------------------------
 // 5-point EPnP (RANSAC kernel): epnp::compute_pose with n = 5, one hypothesis per lane, in
 // two stages so that the workgroup's waves share the work:
@@ -794,6 +822,7 @@ __device__ __forceinline__ void epnp5_eig(const volatile int* sub, const volatil
   }
   double ev4[4][12];
   eig12_small4<28>(mtm, ev4, hh, hs);
+  canon_null2(ev4[0], ev4[1]);
   // hand over (the Householder scratch is dead: eig12_small4 has back-transformed)
 #pragma unroll
   for (int i = 0; i < 4; ++i)
@@ -1328,6 +1357,7 @@ __device__ __forceinline__ void epnp_refit(Shared& sh, const float* p2, const fl
         null4_basis(M, ev4);
       } else {
         eig12_small4<100>(acc, ev4, sh.hh, 1);
+        canon_null2(ev4[0], ev4[1]);
       }
       for (int i = 0; i < 48; ++i) sh.vs[i] = (&ev4[0][0])[i];
       compute_L_6x10(sh.vs, sh.L);
@@ -1984,6 +2014,14 @@ using namespace onepose;
 
 extern "C" {
 
+// The RANSAC and refit kernels keep Shared and the frame's points (2 + 3 floats each) in LDS.
+constexpr size_t kLdsBudget = 160 * 1024;
+constexpr size_t kSharedBytes = ((sizeof(Shared) + 15) / 16) * 16;
+constexpr size_t kPointBytes = 5 * sizeof(float);
+static_assert(kSharedBytes < kLdsBudget, "Shared leaves no room for points");
+
+int onepose_pnp_max_points(void) { return (int)((kLdsBudget - kSharedBytes) / kPointBytes); }
+
 size_t onepose_pnp_workspace_bytes(int batch, int max_points, int max_iters) {
   (void)max_iters;
   if (batch <= 0 || max_points <= 0) return 0;
@@ -1998,8 +2036,10 @@ int onepose_pnp_ransac(const float* pts2d, const float* pts3d, const int* counts
   clear_error();
   OP_REQUIRE(pts2d && pts3d && counts && K && pose34 && inlier_mask && n_inliers && status,
              "pnp: null pointer");
-  OP_REQUIRE(batch >= 1 && max_points >= 1 && max_points <= 8192, "pnp: batch=%d max_points=%d",
-             batch, max_points);
+  OP_REQUIRE(batch >= 1 && max_points >= 1, "pnp: batch=%d max_points=%d", batch, max_points);
+  OP_REQUIRE(max_points <= onepose_pnp_max_points(),
+             "pnp: max_points=%d above onepose_pnp_max_points() = %d (LDS)", max_points,
+             onepose_pnp_max_points());
   OP_REQUIRE(confidence > 0 && confidence < 1, "pnp: confidence %f not in (0,1)", confidence);
   OP_REQUIRE(scale != 0.0, "pnp: scale 0");
   const size_t need = onepose_pnp_workspace_bytes(batch, max_points, max_iters);
@@ -2007,14 +2047,13 @@ int onepose_pnp_ransac(const float* pts2d, const float* pts3d, const int* counts
     set_error("pnp: workspace %zu < %zu bytes", workspace_bytes, need);
     return ONEPOSE_ERR_WORKSPACE;
   }
-  const size_t lds = ((sizeof(Shared) + 15) / 16) * 16 + (size_t)max_points * 5 * sizeof(float);
-  OP_REQUIRE(lds <= 160 * 1024, "pnp: max_points=%d needs %zu B of LDS", max_points, lds);
+  const size_t lds = kSharedBytes + (size_t)max_points * kPointBytes;
   static bool attr_set = false;
   if (!attr_set) {
     OP_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(pnp_ransac_kernel),
-                               hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsBudget));
     OP_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(pnp_refit_kernel),
-                               hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsBudget));
     attr_set = true;
   }
   hipStream_t st = static_cast<hipStream_t>(stream);
@@ -2042,8 +2081,10 @@ int onepose_pose_stage(const int64_t* matches0, const float* kpts2d, int64_t kpt
                  inlier_mask && n_inliers && status,
              "pose_stage: null pointer");
   OP_REQUIRE(!pose_gt || (R_err_deg && t_err_cm && cmd), "pose_stage: null error output");
-  OP_REQUIRE(batch >= 1 && n1 >= 1 && n1 <= 8192 && n3 >= 1, "pose_stage: batch=%d n1=%d n3=%d",
-             batch, n1, n3);
+  OP_REQUIRE(batch >= 1 && n1 >= 1 && n3 >= 1, "pose_stage: batch=%d n1=%d n3=%d", batch, n1, n3);
+  OP_REQUIRE(n1 <= onepose_pnp_max_points(),
+             "pose_stage: n1=%d above onepose_pnp_max_points() = %d (LDS)", n1,
+             onepose_pnp_max_points());
   OP_REQUIRE(confidence > 0 && confidence < 1, "pose_stage: confidence %f not in (0,1)",
              confidence);
   OP_REQUIRE(scale != 0.0, "pose_stage: scale 0");
@@ -2053,14 +2094,13 @@ int onepose_pose_stage(const int64_t* matches0, const float* kpts2d, int64_t kpt
     set_error("pose_stage: workspace %zu < %zu bytes", workspace_bytes, need);
     return ONEPOSE_ERR_WORKSPACE;
   }
-  const size_t lds = ((sizeof(Shared) + 15) / 16) * 16 + (size_t)max_points * 5 * sizeof(float);
-  OP_REQUIRE(lds <= 160 * 1024, "pose_stage: n1=%d needs %zu B of LDS", n1, lds);
+  const size_t lds = kSharedBytes + (size_t)max_points * kPointBytes;
   static bool attr_set = false;
   if (!attr_set) {
     OP_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(pnp_ransac_kernel),
-                               hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsBudget));
     OP_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(pnp_refit_kernel),
-                               hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsBudget));
     attr_set = true;
   }
   hipStream_t st = static_cast<hipStream_t>(stream);

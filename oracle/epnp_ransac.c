@@ -513,6 +513,31 @@ static double compute_R_and_t(Epnp* e, const double* ut, const double* betas, do
   return reprojection_error(e, R, t);
 }
 
+/* Exactly 5 correspondences give M (10 x 12) an exactly 2-dimensional null space, so the two
+ * eigenvectors an eigensolver returns for it are an arbitrary basis of that plane.  Where a
+ * pose fits the five points Gauss-Newton ends at the same model from any basis; where none
+ * does (a RANSAC subset with an outlier in it, a frame solved under the wrong K) its five
+ * fixed iterations do not, and the GPU kernel's eigensolver and the Jacobi sweeps here gave
+ * different models (40 of 150 mask entries on one such frame).  For n == 5 both
+ * implementations turn the pair into a canonical basis of the plane: a = its unit vector
+ * nearest r = the control points' z components (the depths, which dominate a camera-frame
+ * solution), b = a's normal in the plane, signed by the sum of its x components. */
+static void canon_null2(double* a, double* b) {
+  const double al = a[2] + a[5] + a[8] + a[11], be = b[2] + b[5] + b[8] + b[11];
+  const double nrm = sqrt(al * al + be * be);
+  if (!(nrm > 1e-9)) return;
+  const double c = al / nrm, s = be / nrm;
+  double sx = 0.0;
+  for (int k = 0; k < 12; ++k) {
+    const double x = a[k], y = b[k];
+    a[k] = c * x + s * y;
+    b[k] = c * y - s * x;
+    if (k % 3 == 0) sx += b[k];
+  }
+  if (sx < 0.0)
+    for (int k = 0; k < 12; ++k) b[k] = -b[k];
+}
+
 /* Exactly 4 correspondences give M (8 x 12) a 4-dimensional null space, so the basis an
  * eigensolver returns for it -- and with it EPnP's beta approximations -- is arbitrary (it
  * differs between eigensolvers and OpenCV versions).  For n == 4 both implementations here
@@ -617,6 +642,7 @@ void oracle_epnp(const double* pws, const double* us, int n, const double* K, do
   }
   double d[12], ut[144];
   jacobi_eigen(mtm, 12, d, ut);
+  if (n == 5) canon_null2(ut + 12 * 11, ut + 12 * 10);
   if (n == 4) { /* canonical null-space basis (see null4_basis) */
     double M[8][12], v4[4][12];
     for (int i = 0; i < 4; ++i) {

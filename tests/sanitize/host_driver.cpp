@@ -18,7 +18,7 @@ float frand() {
 }  // namespace
 
 int main() {
-  if (onepose_abi_version() != 7) return 1;
+  if (onepose_abi_version() != 8) return 1;
   // matcher packer
   {
     const int n = onepose_matcher_num_tensors();
@@ -96,6 +96,10 @@ int main() {
         }
     }
   }
+  // the solver's size limit: points of 20 B beside its state in 160 KB of LDS
+  const int pnp_max = onepose_pnp_max_points();
+  if (pnp_max < 2048 || pnp_max >= 8192) return 10;
+  acc += onepose_pnp_workspace_bytes(1, pnp_max, 10000);
   acc += onepose_superpoint_workspace_bytes(1, 512, 512) + onepose_superpoint_detect_workspace_bytes(2, 480, 640);
   std::printf("size queries ok (%zu)\n", acc);
   return 0;

@@ -30,7 +30,7 @@ def test_library_exports_every_header_symbol():
     missing = [s for s in header_symbols() if not hasattr(lib, s)]
     assert not missing, missing
     assert set(header_symbols()) == set(_lib.PROTOTYPES), "ctypes prototypes out of sync"
-    assert lib.onepose_abi_version() == _lib.ABI_VERSION == 7
+    assert lib.onepose_abi_version() == _lib.ABI_VERSION == 8
 
 
 def test_object_cache_size_follows_its_flags():
@@ -191,6 +191,35 @@ def test_object_cache_size_per_precision():
             assert full - lib.onepose_object_cache_bytes_ex(n3, 8, flags, PRECISIONS["fp32"]) == 1536 * n3
     assert lib.onepose_object_cache_bytes_ex(16, 8, 0, 9) == 0
     assert lib.onepose_pnp_workspace_bytes(2, 1024, 10000) >= 2 * 1024 * 4
+
+
+def test_pnp_max_points_is_checked_on_the_host():
+    """onepose_pnp_max_points (ABI 8): the solver keeps its state and 20 B per point in a
+    workgroup's 160 KB of LDS, so the limit lies below 8192 (8192 points alone are 160 KB) and
+    above config 5's n1 = 2048.  Both entry points refuse one more point with
+    ONEPOSE_ERR_INVALID before touching an argument; at the limit they get as far as the
+    workspace check (a null workspace: ONEPOSE_ERR_WORKSPACE), still without a launch."""
+    from onepose_amd import _lib
+    lib = _lib.load()
+    limit = lib.onepose_pnp_max_points()
+    assert 2048 < limit < 8192
+    buf = np.zeros(16)
+    p = buf.ctypes.data   # non-null; never dereferenced by a call that is refused
+
+    def ransac(m):
+        return lib.onepose_pnp_ransac(p, p, p, m, p, 0, 1, 1000.0, 5.0, 100, 0.99, p, p, p, p,
+                                      None, 0, None)
+
+    def stage(n1):
+        return lib.onepose_pose_stage(p, p, 0, p, 0, 1, n1, 8, 1000.0, p, 0, 5.0, 100, 0.99,
+                                      None, 0, p, p, p, p, p, p, p, None, None, None, None, 0,
+                                      None)
+    for call in (ransac, stage):
+        rc_over = call(limit + 1)
+        assert rc_over != 0 and b"onepose_pnp_max_points" in lib.onepose_last_error()
+        rc_at = call(limit)
+        assert rc_at not in (0, rc_over) and b"workspace" in lib.onepose_last_error()
+        assert call(8192) == rc_over and call(0) == rc_over
 
 
 def test_module_state_dict_keys_match_reference():

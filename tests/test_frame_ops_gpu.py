@@ -45,6 +45,112 @@ def test_select_correspondences(device):
         np.testing.assert_array_equal(p3[b, :cnt[b]], r3)
 
 
+@pytest.mark.parametrize("per_frame_table", [False, True])
+@pytest.mark.parametrize("n1", [1, 1023, 1024, 1025, 2500])
+def test_select_correspondences_chunks_strides_and_bad_indices(n1, per_frame_table, device):
+    """The kernel scans 1024 matches per trip: one trip short of, on and past a full chunk, and
+    three trips; a 3D table per frame ([B,n3,3], kp3_bs = 3 n3) and the shared one (0); frames
+    that are all valid, none valid, valid at index 0 and n1 - 1 only; and indices outside the
+    table (n3, n3 + 7, -2), which are dropped like -1.  Exact."""
+    rs = np.random.RandomState(10 + n1)
+    B, n3 = 5, 300
+    m0 = np.where(rs.rand(B, n1) < 0.4, rs.randint(0, n3, (B, n1)), -1).astype(np.int64)
+    m0[1] = rs.randint(0, n3, n1)          # all valid
+    m0[2] = -1                             # none valid
+    m0[3] = -1
+    m0[3, 0], m0[3, n1 - 1] = n3 - 1, 0    # the first and the last entry only
+    clean = m0.copy()
+    for b in (0, 4):                       # plant indices outside the table
+        bad = rs.choice(n1, min(n1, 40), replace=False)
+        m0[b, bad] = rs.choice([n3, n3 + 7, -2], bad.size)
+        clean[b, bad] = -1
+    kp2 = rs.uniform(0, 512, (B, n1, 2)).astype(np.float32)
+    kp3 = rs.uniform(-0.1, 0.1, (B, n3, 3)).astype(np.float32)
+    if not per_frame_table:
+        kp3 = kp3[0]
+    p2, p3, cnt = P.select_correspondences(torch.from_numpy(m0).to(device),
+                                           torch.from_numpy(kp2).to(device),
+                                           torch.from_numpy(kp3).to(device), scale=1000.0)
+    p2, p3, cnt = p2.cpu().numpy(), p3.cpu().numpy(), cnt.cpu().numpy()
+    for b in range(B):
+        r2, r3 = O.select_correspondences(clean[b], kp2[b], kp3[b] if per_frame_table else kp3,
+                                          1000.0)
+        assert cnt[b] == r2.shape[0], b
+        np.testing.assert_array_equal(p2[b, :cnt[b]], r2)
+        np.testing.assert_array_equal(p3[b, :cnt[b]], r3)
+    assert cnt[1] == n1 and cnt[2] == 0 and cnt[3] == min(n1, 2)
+
+
+def _rot(axis, deg):
+    axis = np.asarray(axis, np.float64) / np.linalg.norm(axis)
+    a = np.deg2rad(deg)
+    Kx = np.array([[0, -axis[2], axis[1]], [axis[2], 0, -axis[0]], [-axis[1], axis[0], 0]])
+    return np.eye(3) + np.sin(a) * Kx + (1 - np.cos(a)) * Kx @ Kx
+
+
+@pytest.fixture(scope="module")
+def error_cases():
+    """130 (pred, gt) pairs (more than two 64-thread groups) and the oracle's errors for them,
+    per-frame gt and gt[0] shared.  arccos is ill-conditioned at trace 3 and trace -1, where
+    one ulp of the trace moves the angle by 1e-6 deg and the summation order decides (the
+    reference itself is rounding-dependent there), so the cases at those points are built to be
+    the same in any order: rotations with entries 0 and +-1 (a prediction equal to its gt; a
+    180 deg turn), a pair whose entries are scaled by 1 + 2^-50 (the trace lands above 3 and is
+    clamped: 0 deg) and one turned 180 deg and scaled the same (below -1: NaN, as the
+    reference).  The random pairs lie 0.1 to 179 deg apart."""
+    rs = np.random.RandomState(3)
+    from onepose_amd import synthetic as S
+    B = 130
+    gts, preds = np.zeros((B, 3, 4)), np.zeros((B, 3, 4))
+    for b in range(B):
+        Rg = S.random_rotation(rs)
+        tg = rs.uniform(-0.1, 0.1, 3) + np.array([0, 0, 0.5])
+        ang = [0.1, 0.9, 1.1, 2.9, 3.1, 4.9, 5.1, 30.0, 120.0, 179.0][b % 10]
+        Rp = _rot(rs.standard_normal(3), ang) @ Rg
+        tp = tg + rs.standard_normal(3) * [0.002, 0.02, 0.06][b % 3]
+        gts[b], preds[b] = np.c_[Rg, tg], np.c_[Rp, tp]
+    perm = np.array([[0.0, -1.0, 0.0], [0.0, 0.0, 1.0], [-1.0, 0.0, 0.0]])   # det +1
+    flip = np.diag([1.0, -1.0, -1.0])
+    up = 1.0 + 2.0 ** -50
+    for b, (Rp, Rg) in {0: (perm, perm), 64: (np.eye(3), np.eye(3)), 129: (perm, perm),
+                        1: (flip @ perm, perm), 65: (perm * up, perm * up),
+                        128: (flip @ perm * up, perm * up)}.items():
+        preds[b, :, :3], gts[b, :, :3] = Rp, Rg
+    preds[0, :, 3] = gts[0, :, 3]
+    with np.errstate(invalid="ignore"):
+        own = np.array([O.pose_error(preds[b], gts[b]) for b in range(B)])
+        shared = np.array([O.pose_error(preds[b], gts[0]) for b in range(B)])
+    assert own[0].tolist() == [0.0, 0.0] and own[64, 0] == 0.0 and own[65, 0] == 0.0
+    assert own[1, 0] == 180.0 and np.isnan(own[128, 0]) and np.isnan(own[:, 0]).sum() == 1
+    for o in (own, shared):
+        o.setflags(write=False)
+    return preds, gts, own, shared
+
+
+@pytest.mark.parametrize("gt_form", ["per_frame", "shared", "homogeneous"])
+def test_pose_errors_strides_and_branch_points(gt_form, error_cases, device):
+    """pose_errors over 130 frames with gt [B,3,4], one shared [3,4] (gt_bstride 0) and
+    [B,4,4]: within 1e-9 of the oracle, NaN exactly where the oracle has NaN, and the 1/3/5
+    cm-deg flags equal to the thresholds applied to the oracle's numbers."""
+    preds, gts, own, shared = error_cases
+    want = shared if gt_form == "shared" else own
+    gt = {"per_frame": gts, "shared": gts[0],
+          "homogeneous": np.concatenate([gts, np.tile([[[0.0, 0.0, 0.0, 1.0]]], (130, 1, 1))],
+                                        1)}[gt_form]
+    r, t, cmd = P.pose_errors(torch.from_numpy(preds).to(device), torch.from_numpy(gt).to(device))
+    r, t, cmd = r.cpu().numpy(), t.cpu().numpy(), cmd.cpu().numpy().astype(bool)
+    nan = np.isnan(want[:, 0])
+    np.testing.assert_array_equal(np.isnan(r), nan)
+    assert not np.isnan(t).any()
+    assert np.abs(r[~nan] - want[~nan, 0]).max() < 1e-9
+    assert np.abs(t - want[:, 1]).max() < 1e-9
+    with np.errstate(invalid="ignore"):
+        for i, lim in enumerate((1.0, 3.0, 5.0)):
+            np.testing.assert_array_equal(cmd[:, i], (want[:, 1] < lim) & (want[:, 0] < lim))
+    if gt_form != "shared":
+        assert cmd.any(0).all() and not cmd.all(0).any()   # every flag takes both values
+
+
 def test_pose_errors_match_reference_evaluator(device):
     g = golden("evaluator")
     preds = torch.from_numpy(g["preds"]).to(device)

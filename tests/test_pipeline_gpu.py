@@ -96,6 +96,74 @@ def test_fused_pose_stage_matches_separate_calls(setup):
             np.testing.assert_array_equal(o.pts3d[b, :c].cpu().numpy(), sep["pts3d"][b, :c])
         _assert_same(sep_core := {k: sep[k] for k in fused}, fused)
         assert sep_core["status"].tolist() == [0] * B
+    _fused_stage_per_frame_everything(pipe.device)
+
+
+def _fused_stage_per_frame_everything(dev):
+    """The same demand on what the pipeline never varies: 4 frames, each with its own K
+    (fx != fy, cx != cy), ground truth and 3D table (kpts3d_bstride = 3 n3), n1 = 1100 (more
+    than four 256-thread trips of the in-kernel scan), reprojection error 3 and a cap of 100
+    iterations; the last frame keeps 3 matches (status 1: the identity pose and its errors)."""
+    from onepose_amd import _lib
+    from onepose_amd import pose as P
+    rs = np.random.RandomState(21)
+    nb, n1, n3 = 4, 1100, 1500
+    Ks = np.stack([np.array([[640.0, 0, 231.5], [0, 565.0, 287.25], [0, 0, 1]]),
+                   np.array([[310.0, 0, 100.0], [0, 295.0, 140.0], [0, 0, 1]]),
+                   synthetic.crop_intrinsics(),
+                   np.array([[480.0, 0, 300.0], [0, 520.0, 200.0], [0, 0, 1]])])
+    kp3 = rs.uniform(-0.1, 0.1, (nb, n3, 3)).astype(np.float32)
+    m0 = np.where(rs.rand(nb, n1) < 0.5, rs.randint(0, n3, (nb, n1)), -1).astype(np.int64)
+    m0[3] = -1
+    m0[3, [5, 600, n1 - 1]] = [7, 8, 9]
+    kp2 = rs.uniform(0, 512, (nb, n1, 2)).astype(np.float32)
+    gts = np.zeros((nb, 3, 4))
+    for b in range(nb):
+        R = synthetic.random_rotation(rs)
+        t = np.array([rs.uniform(-0.03, 0.03), rs.uniform(-0.03, 0.03), rs.uniform(0.35, 0.55)])
+        pose = np.concatenate([R, t[:, None]], 1)
+        good = (m0[b] > -1) & (rs.rand(n1) < 0.7)      # the rest of the matches are wrong
+        uv = synthetic.project(Ks[b], pose, kp3[b, m0[b, good]].astype(np.float64))
+        kp2[b, good] = (uv + rs.normal(0, 0.5, uv.shape)).astype(np.float32)
+        pose[:, 3] += rs.normal(0, 0.004, 3)           # a gt a little off: non-trivial errors
+        gts[b] = pose
+    m0_d, kp2_d, kp3_d = (torch.from_numpy(x).to(dev) for x in (m0, kp2, kp3))
+    K_d, gt_d = torch.from_numpy(Ks).to(dev), torch.from_numpy(gts).to(dev)
+    p2, p3, counts = P.select_correspondences(m0_d, kp2_d, kp3_d, scale=1000.0)
+    pose, mask, nin, status = P.ransac_pnp_batch(p2, p3, counts, K_d, scale=1000.0,
+                                                 reprojection_error=3.0, iterations_count=100)
+    r, t, cmd = P.pose_errors(pose, gt_d)
+    torch.cuda.synchronize()
+    sep = dict(pose=pose, inlier_mask=mask, n_inliers=nin, status=status, R_err=r, t_err=t,
+               cmd=cmd, counts=counts)
+    assert status.tolist() == [0, 0, 0, 1] and counts.tolist()[3] == 3
+    assert min(counts.tolist()[:3]) > 400 and min(nin.tolist()[:3]) > 200
+    lib = _lib.load()
+    f = dict(pts2d=torch.zeros(nb, n1, 2, device=dev), pts3d=torch.zeros(nb, n1, 3, device=dev),
+             counts=torch.zeros(nb, dtype=torch.int32, device=dev),
+             pose=torch.zeros(nb, 3, 4, dtype=torch.float64, device=dev),
+             inlier_mask=torch.zeros(nb, n1, dtype=torch.uint8, device=dev),
+             n_inliers=torch.zeros(nb, dtype=torch.int32, device=dev),
+             status=torch.full((nb,), -1, dtype=torch.int32, device=dev),
+             R_err=torch.zeros(nb, dtype=torch.float64, device=dev),
+             t_err=torch.zeros(nb, dtype=torch.float64, device=dev),
+             cmd=torch.zeros(nb, 3, dtype=torch.uint8, device=dev))
+    ws_bytes = lib.onepose_pnp_workspace_bytes(nb, n1, 100)
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+    _lib.check(lib.onepose_pose_stage(
+        m0_d.data_ptr(), kp2_d.data_ptr(), n1 * 2, kp3_d.data_ptr(), n3 * 3, nb, n1, n3, 1000.0,
+        K_d.data_ptr(), 9, 3.0, 100, 0.99, gt_d.data_ptr(), 12, f["pts2d"].data_ptr(),
+        f["pts3d"].data_ptr(), f["counts"].data_ptr(), f["pose"].data_ptr(),
+        f["inlier_mask"].data_ptr(), f["n_inliers"].data_ptr(), f["status"].data_ptr(),
+        f["R_err"].data_ptr(), f["t_err"].data_ptr(), f["cmd"].data_ptr(), ws.data_ptr(),
+        ws_bytes, _lib.stream_ptr(dev)), "pose_stage")
+    torch.cuda.synchronize()
+    for k, v in sep.items():
+        np.testing.assert_array_equal(f[k].cpu().numpy(), v.cpu().numpy(), err_msg=k)
+    for b in range(nb):
+        c = int(counts[b])
+        np.testing.assert_array_equal(f["pts2d"][b, :c].cpu().numpy(), p2[b, :c].cpu().numpy())
+        np.testing.assert_array_equal(f["pts3d"][b, :c].cpu().numpy(), p3[b, :c].cpu().numpy())
 
 
 @pytest.mark.gpu

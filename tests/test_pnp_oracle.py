@@ -13,9 +13,16 @@ from onepose_amd import synthetic as S
 from oracle import pnp_oracle as O
 
 
-def scene(seed, n, outlier_frac=0.3, px_noise=0.0):
+# Intrinsics with fx != fy and cx != cy, as real OnePose crops have: under crop_intrinsics()
+# (fx = fy, cx = cy) a solver that swaps the focal lengths or the principal point's
+# coordinates gives the same answer.
+K_A = np.array([[640.0, 0.0, 231.5], [0.0, 565.0, 287.25], [0.0, 0.0, 1.0]])
+K_B = np.array([[310.0, 0.0, 100.0], [0.0, 295.0, 140.0], [0.0, 0.0, 1.0]])
+
+
+def scene(seed, n, outlier_frac=0.3, px_noise=0.0, K=None):
     rs = np.random.RandomState(seed)
-    K = S.crop_intrinsics()
+    K = S.crop_intrinsics() if K is None else np.array(K, np.float64)
     R = S.random_rotation(rs)
     t = np.array([rs.uniform(-0.03, 0.03), rs.uniform(-0.03, 0.03), rs.uniform(0.35, 0.55)])
     pose = np.concatenate([R, t[:, None]], 1)
@@ -59,6 +66,76 @@ def test_ransac_exact_scene_recovers_pose_and_inliers(seed, outliers):
     assert nin == near.sum()
     assert rot_err(est[:, :3], pose[:, :3]) < 1e-4       # north-star bound, radians
     assert np.linalg.norm(est[:, 3] - pose[:, 3]) < 1e-3
+
+
+def swap_focal(K):
+    K = K.copy()
+    K[0, 0], K[1, 1] = K[1, 1], K[0, 0]
+    return K
+
+
+def swap_centre(K):
+    K = K.copy()
+    K[0, 2], K[1, 2] = K[1, 2], K[0, 2]
+    return K
+
+
+@pytest.mark.parametrize("n", [6, 12, 50])
+def test_epnp_exact_correspondences_asymmetric_K(n):
+    p2, p3, K, pose, _ = scene(11 + n, n, outlier_frac=0.0, K=K_A)
+    R, t = O.epnp(p3.astype(np.float64), p2.astype(np.float64), K)
+    assert rot_err(R, pose[:, :3]) < 1e-5
+    assert np.linalg.norm(t - pose[:, 3]) < 1e-5
+
+
+@pytest.mark.parametrize("seed", [1, 2])
+@pytest.mark.parametrize("Kname", ["K_A", "K_B"])
+def test_ransac_exact_scene_asymmetric_K(Kname, seed):
+    """Exact data under fx != fy, cx != cy: the true pose and inlier set.  The control: the
+    same points solved with the focal lengths swapped, and with the principal point's
+    coordinates swapped, land more than a degree away (2.1 to 10.6 deg over these eight runs,
+    against 3e-6 deg unswapped; under crop_intrinsics() both swaps change nothing), so these
+    scenes see an oracle that mixes up the rows of K."""
+    p2, p3, K, pose, near = scene(seed, 300, outlier_frac=0.3, K={"K_A": K_A, "K_B": K_B}[Kname])
+    st, est, mask, nin, _ = O.pnp_ransac(p2, p3 * 1000.0, K, scale=1000.0)
+    assert st == 0
+    np.testing.assert_array_equal(mask, near)
+    assert nin == near.sum()
+    assert rot_err(est[:, :3], pose[:, :3]) < 1e-4       # north-star bound, radians
+    assert np.linalg.norm(est[:, 3] - pose[:, 3]) < 1e-3
+    for swapped in (swap_focal(K), swap_centre(K)):
+        _, bad, _, _, _ = O.pnp_ransac(p2, p3 * 1000.0, swapped, scale=1000.0)
+        assert np.degrees(rot_err(bad[:, :3], pose[:, :3])) > 1.0
+    K0 = S.crop_intrinsics()   # why the old scenes could not see it
+    np.testing.assert_array_equal(swap_focal(K0), K0)
+    np.testing.assert_array_equal(swap_centre(K0), K0)
+
+
+def test_ransac_parameter_sweep_reaches_its_paths():
+    """tests/test_pnp_gpu.py sweeps iterations_count x reprojection_error x confidence over two
+    noisy 300-point scenes (seed 5, K_A, 30% and 60% outliers) to reach the kernel's stopping
+    paths: a cap inside a 64-iteration round and on its boundary, the confidence rule stopping
+    early, a cap that leaves no model, and runs of dozens of rounds.  The oracle's
+    iterations_run must keep taking these values, or the sweep has stopped reaching them."""
+    scenes = [scene(5, 300, f, 0.5, K=K_A) for f in (0.3, 0.6)]
+    iters, status = {}, {}
+    for cap in (1, 10, 63, 64, 65, 100, 10000):
+        for reproj in (1.0, 5.0, 20.0):
+            for conf in (0.5, 0.99, 0.999999):
+                for f, (p2, p3, K, _, _) in zip((0.3, 0.6), scenes):
+                    st, _, _, _, it = O.pnp_ransac(p2, p3 * 1000.0, K, 1000.0, reproj, cap, conf)
+                    iters[cap, reproj, conf, f], status[cap, reproj, conf, f] = it, st
+    assert {1, 5, 31, 63, 64, 65, 128} <= set(iters.values())
+    assert max(iters.values()) > 64 * 40
+    assert iters[10000, 1.0, 0.99, 0.6] == 2839 and iters[10000, 1.0, 0.999999, 0.6] == 5678
+    assert iters[10000, 5.0, 0.5, 0.3] == 5 and iters[10000, 5.0, 0.99, 0.3] == 31
+    assert iters[10000, 1.0, 0.99, 0.3] == 128            # exactly two rounds
+    for cap in (10, 63, 64, 65, 100):   # the cap, mid-round and on the boundary; no model at 60%
+        assert iters[cap, 1.0, 0.99, 0.3] == cap and status[cap, 1.0, 0.99, 0.3] == 0
+        for reproj in (1.0, 5.0):
+            assert iters[cap, reproj, 0.99, 0.6] == cap and status[cap, reproj, 0.99, 0.6] == 2
+    assert all(status[1, r, c, f] == 2 for r in (1.0, 5.0, 20.0) for c in (0.5, 0.99, 0.999999)
+               for f in (0.3, 0.6))
 
 
 def test_ransac_noisy_scene_is_noise_limited():

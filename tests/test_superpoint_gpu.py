@@ -49,6 +49,38 @@ def test_detect_tail_bit_exact_on_reference_maps(tag, device):
 
 
 @pytest.mark.parametrize("tag", sorted(CASES))
+def test_detect_tail_align_corners_without_border(tag, device):
+    """The sampler's align_corners=True branch (the reference takes it under torch 1.3 and
+    later 1.x releases; every other test here passes False) on the reference's maps, with no
+    border removed: keypoints sit in the first and last rows and columns, where the bilinear
+    corners fall outside the map and are dropped.  Keypoints and scores exact against the
+    oracle tail, descriptors against its sampler."""
+    _, _, _, max_kp = CASES[tag]
+    g = golden("superpoint")
+    smap, dense = g[f"{tag}_score_map"], g[f"{tag}_dense_desc"]
+    raw = detect_from_maps(torch.from_numpy(smap)[None].to(device),
+                           torch.from_numpy(dense).permute(1, 2, 0)[None].contiguous().to(device),
+                           nms_radius=3, keypoint_threshold=0.005, remove_borders=0,
+                           max_keypoints=max_kp, align_corners=True)
+    kp, sc, desc, n = first(raw)
+    kp_o, sc_o = O.select_keypoints(O.simple_nms(smap, 3), 0.005, 0, max_kp)
+    h, w = smap.shape
+    # a first row or column (a corner at -1) and a last one (a corner at h / 8 or w / 8)
+    assert ((kp_o[:, 0] == 0) | (kp_o[:, 1] == 0)).any()
+    assert ((kp_o[:, 0] == w - 1) | (kp_o[:, 1] == h - 1)).any()
+    np.testing.assert_array_equal(kp, kp_o)
+    np.testing.assert_array_equal(sc, sc_o)
+    d_o = O.sample_descriptors(kp_o[None], dense[None], 8, True)[0]
+    np.testing.assert_allclose(desc, d_o, atol=1e-6)
+    d_false = O.sample_descriptors(kp_o[None], dense[None], 8, False)[0]
+    assert np.abs(d_o - d_false).max() > 1e-3      # the two branches differ on these keypoints
+    k = raw["keypoints"].shape[1]
+    assert (n < k) == (tag == "sq")
+    if n < k:   # capacity past the count is zero-filled
+        assert not raw["keypoints"][0, n:].any() and not raw["descriptors"][0, :, n:].any()
+
+
+@pytest.mark.parametrize("tag", sorted(CASES))
 def test_end_to_end_matches_reference(tag, device):
     h, w, seed, max_kp = CASES[tag]
     g = golden("superpoint")
