@@ -483,7 +483,68 @@ int onepose_superpoint_detect(const float* score_map, const float* dense_desc, i
                               size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------ *
- * Measurement hook (bench.py's roofline).  While enabled, every launch whose kernel kind
+ * SuperGlue 2D-2D matcher  --  replaces SuperGlue.forward
+ *   (src/models/matchers/SuperGlue/superglue.py:264-327: the keypoint encoder, 18 softmax
+ *    attention layers, the final projection, log_optimal_transport and the mutual check;
+ *    reached from inference_demo.py's LocalFeatureObjectDetector and src/sfm/match_features.py)
+ * fp32 only.  This family is versioned on its own: onepose_superglue_version() returns 1 and
+ * is bumped when one of the entry points below changes, while onepose_abi_version() stays 8 --
+ * nothing that existed at ABI 8 changed, and a caller of the GATsSPG / pose entry points need
+ * not rebuild for a matcher it does not use.
+ * ------------------------------------------------------------------------------------ */
+int onepose_superglue_version(void);
+/* The packer, as the GATsSPG matcher's: tensor i's reference state-dict key (the BatchNorm
+ * weight / bias / running_mean / running_var and bin_score included; num_batches_tracked is
+ * not consumed) and element count; float32 host tensors in that order -> one device-ready
+ * panel.  Packing folds each eval-mode BatchNorm into the convolution before it, permutes
+ * q/k/v (and the merge convolution's inputs) to head-major channels (the reference's
+ * .view(B, 64, 4, N) makes channel c = d*4 + h) and folds the merge convolution into the
+ * message half of MLP conv 1. */
+int onepose_superglue_num_tensors(void);
+const char* onepose_superglue_tensor_name(int i);
+int64_t onepose_superglue_tensor_numel(int i);
+size_t onepose_superglue_packed_bytes(void);
+int onepose_superglue_pack(const float* const* tensors, int n_tensors, void* packed_host);
+/* Workspace bytes of one forward (0 for a shape the forward refuses). */
+size_t onepose_superglue_workspace_bytes(int batch, int n0, int n1);
+/* One forward over `batch` pairs.  Per image i: desc_i [batch, 256, n_i], kpts_i [batch, n_i, 2]
+ * (x, y pixels), scores_i [batch, n_i], each with a batch stride in elements; stride 0 = the
+ * tensor is shared by the batch (one query against many views).  h_i, w_i: the image sizes
+ * normalize_keypoints reads (:67-84).  sinkhorn_iters >= 0 and match_threshold are the
+ * reference's config entries.  precision: ONEPOSE_PREC_FP32 only (others:
+ * ONEPOSE_ERR_UNSUPPORTED).  Outputs matches0 [batch, n0] / matches1 [batch, n1] int64 (-1 = no
+ * match), mscores0 / mscores1 fp32; log_assignment [batch, n0+1, n1+1] fp32 or NULL: the
+ * reference's `scores` after log_optimal_transport.  1 <= n0, n1 <= 16384 (the caller handles
+ * the empty branch, :269-276).  All device pointers; the workspace 256-byte aligned. */
+int onepose_superglue_match(const void* packed_weights,
+                            const float* desc0, int64_t desc0_bstride,
+                            const float* kpts0, int64_t kpts0_bstride,
+                            const float* scores0, int64_t scores0_bstride,
+                            const float* desc1, int64_t desc1_bstride,
+                            const float* kpts1, int64_t kpts1_bstride,
+                            const float* scores1, int64_t scores1_bstride,
+                            int batch, int n0, int n1, int h0, int w0, int h1, int w1,
+                            int sinkhorn_iters, float match_threshold, int precision,
+                            int64_t* matches0, int64_t* matches1, float* mscores0,
+                            float* mscores1, float* log_assignment, void* workspace,
+                            size_t workspace_bytes, void* stream);
+/* log_optimal_transport alone (:190-210): scores [batch, m, n] (bstride elements) with the
+ * dustbin score alpha -> out [batch, m+1, n+1] = Z + u + v - norm after `iters` >= 0 log-space
+ * Sinkhorn iterations.  Deterministic: no atomics, every merge in a fixed order. */
+size_t onepose_log_optimal_transport_workspace_bytes(int batch, int m, int n);
+int onepose_log_optimal_transport(const float* scores, int64_t scores_bstride, int batch, int m,
+                                  int n, float alpha, int iters, float* out, void* workspace,
+                                  size_t workspace_bytes, void* stream);
+/* Multi-head softmax attention alone (:103-119): q [batch, n, 256], k, v [batch, m, 256],
+ * token-major with head-major channels (4 heads x 64) -> out [batch, n, 256] =
+ * softmax(q k^T / 8) v per head.  Batch strides in elements (multiples of 4; 0 = shared input);
+ * pointers 16-byte aligned. */
+int onepose_mha_softmax(const float* q, int64_t q_bstride, const float* k, int64_t k_bstride,
+                        const float* v, int64_t v_bstride, int batch, int n, int m, float* out,
+                        int64_t out_bstride, void* stream);
+
+/* ------------------------------------------------------------------------------------ *
+ * Measurement hook (bench.py's roofline). While enabled, every launch whose kernel kind
  * is in `kind_mask` (bit k = kind k, names from onepose_profile_kind_name) is bracketed by
  * two HIP events recorded on the launch's own stream.  Host-side state, not for use during
  * graph capture.  _end synchronises and returns, per bracketed launch, its kind and the

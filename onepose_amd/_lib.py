@@ -129,6 +129,25 @@ PROTOTYPES = {
     "onepose_superpoint_detect": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_float,
                                           c_int, c_int, c_int, c_void_p, c_void_p, c_void_p,
                                           c_void_p, c_void_p, c_size_t, c_void_p]),
+    "onepose_superglue_version": (c_int, []),
+    "onepose_superglue_num_tensors": (c_int, []),
+    "onepose_superglue_tensor_name": (c_char_p, [c_int]),
+    "onepose_superglue_tensor_numel": (c_int64, [c_int]),
+    "onepose_superglue_packed_bytes": (c_size_t, []),
+    "onepose_superglue_pack": (c_int, [ctypes.POINTER(c_void_p), c_int, c_void_p]),
+    "onepose_superglue_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "onepose_superglue_match": (c_int, [c_void_p,
+                                        c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64,
+                                        c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64,
+                                        c_int, c_int, c_int, c_int, c_int, c_int, c_int,
+                                        c_int, c_float, c_int,
+                                        c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                        c_void_p, c_size_t, c_void_p]),
+    "onepose_log_optimal_transport_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "onepose_log_optimal_transport": (c_int, [c_void_p, c_int64, c_int, c_int, c_int, c_float,
+                                              c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "onepose_mha_softmax": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64,
+                                    c_int, c_int, c_int, c_void_p, c_int64, c_void_p]),
     "onepose_profile_begin": (c_int, [ctypes.c_uint64, c_int]),
     "onepose_profile_begin_device": (c_int, [ctypes.c_uint64]),
     "onepose_profile_end_device": (c_int, [c_void_p, c_void_p, c_int]),

@@ -122,7 +122,8 @@ const char* kKindNames[K_NUM_KINDS] = {
     "transpose_in", "gat", "qkv_gemm", "kv_reduce", "m_fold", "mlp1_gemm",
     "stats_finalize", "mlp2_gemm", "final_gemm", "l2norm", "score_gemm", "softmax_reduce",
     "conf", "mutual", "select", "pnp_ransac", "pnp_refit", "pose_error", "sample_desc",
-    "sp_conv", "sp_nms", "sp_select", "sp_desc"};
+    "sp_conv", "sp_nms", "sp_select", "sp_desc", "sg_input", "sg_attention", "sg_sinkhorn",
+    "sg_match"};
 }  // namespace
 
 StampAcc* prof_stamp_slot(int kind) {

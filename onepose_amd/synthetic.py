@@ -298,3 +298,110 @@ def superpoint_image(h: int, w: int, seed: int = 0) -> np.ndarray:
     img += 0.05 * rs.randn(h, w)
     img = (img - img.min()) / (img.max() - img.min())
     return img.astype(np.float32)
+
+
+# ---------------------------------------------------------------------------------------
+# SuperGlue 2D-2D matcher (src/models/matchers/SuperGlue/superglue.py)
+# ---------------------------------------------------------------------------------------
+SUPERGLUE_KENC = (32, 64, 128, 256)     # default_config['keypoint_encoder'] (superglue.py:241)
+SUPERGLUE_LAYERS = 18                   # ['self', 'cross'] * 9 (:242)
+SUPERGLUE_IMAGE = 512                   # make_superglue_inputs' image side
+
+
+def _bn_stats(rs, sd, prefix, c):
+    # eval-mode BatchNorm1d: default affine (1, 0), running statistics randomised so the fold
+    # into the preceding convolution is exercised
+    sd[f"{prefix}.weight"] = np.ones(c, np.float32)
+    sd[f"{prefix}.bias"] = np.zeros(c, np.float32)
+    sd[f"{prefix}.running_mean"] = (0.1 * rs.standard_normal(c)).astype(np.float32)
+    sd[f"{prefix}.running_var"] = rs.uniform(0.5, 1.5, size=c).astype(np.float32)
+    sd[f"{prefix}.num_batches_tracked"] = np.array(0, dtype=np.int64)
+
+
+def superglue_state_dict(seed: int = 0, well_conditioned: bool = True) -> dict[str, np.ndarray]:
+    """A full ``SuperGlue`` state dict with the reference's keys and shapes (superglue.py:247-262):
+    torch-default conv initialisation, randomised BatchNorm running statistics; with
+    ``well_conditioned`` the last conv of every layer's MLP is scaled by 0.3 and ``final_proj``
+    is 20 x a random orthogonal matrix with zero bias, so the matcher produces real matches."""
+    rs = np.random.RandomState(seed)
+    sd: dict[str, np.ndarray] = {"bin_score": np.array(1.0, dtype=np.float32)}
+    chans = [3, *SUPERGLUE_KENC, DESC_DIM]
+    for j in range(len(chans) - 1):
+        w, b = _conv_default(rs, chans[j + 1], chans[j])
+        if j == len(chans) - 2:
+            b[:] = 0.0                                   # superglue.py:96
+        sd[f"kenc.encoder.{3 * j}.weight"], sd[f"kenc.encoder.{3 * j}.bias"] = w, b
+        if j < len(chans) - 2:
+            _bn_stats(rs, sd, f"kenc.encoder.{3 * j + 1}", chans[j + 1])
+    for i in range(SUPERGLUE_LAYERS):
+        p = f"gnn.layers.{i}"
+        w, b = _conv_default(rs, DESC_DIM, DESC_DIM)
+        sd[f"{p}.attn.merge.weight"], sd[f"{p}.attn.merge.bias"] = w, b
+        for j in range(3):
+            w, b = _conv_default(rs, DESC_DIM, DESC_DIM)
+            sd[f"{p}.attn.proj.{j}.weight"], sd[f"{p}.attn.proj.{j}.bias"] = w, b
+        w, b = _conv_default(rs, 2 * DESC_DIM, 2 * DESC_DIM)
+        sd[f"{p}.mlp.0.weight"], sd[f"{p}.mlp.0.bias"] = w, b
+        _bn_stats(rs, sd, f"{p}.mlp.1", 2 * DESC_DIM)
+        w, b = _conv_default(rs, DESC_DIM, 2 * DESC_DIM)
+        b[:] = 0.0                                       # superglue.py:155
+        if well_conditioned:
+            w *= np.float32(0.3)
+        sd[f"{p}.mlp.3.weight"], sd[f"{p}.mlp.3.bias"] = w, b
+    w, b = _conv_default(rs, DESC_DIM, DESC_DIM)
+    if well_conditioned:
+        q, r = np.linalg.qr(rs.standard_normal((DESC_DIM, DESC_DIM)))
+        q = q * np.sign(np.diag(r))[None, :]
+        w = (20.0 * q).astype(np.float32)[:, :, None]
+        b = np.zeros(DESC_DIM, np.float32)
+    sd["final_proj.weight"], sd["final_proj.bias"] = w, b
+    return sd
+
+
+def _sg_derive(rs, kp, desc, n):
+    """n points of another view of (kp [k,2], desc [k,256]): a random subset (n <= k) or a
+    resampling, with 2 px keypoint noise and 0.03 descriptor noise; one third replaced by
+    random outliers."""
+    k = kp.shape[0]
+    idx = rs.permutation(k)[:n] if n <= k else rs.randint(0, k, size=n)
+    kp1 = kp[idx] + 2.0 * rs.standard_normal((n, 2))
+    d1 = _unit_rows(desc[idx] + 0.03 * rs.standard_normal((n, DESC_DIM)))
+    out = rs.permutation(n)[: n // 3]
+    kp1[out] = rs.uniform(0, SUPERGLUE_IMAGE, size=(len(out), 2))
+    d1[out] = _unit_rows(rs.standard_normal((len(out), DESC_DIM)))
+    return kp1, d1
+
+
+def make_superglue_inputs(n0: int, n1: int, seed: int = 0, batch: int = 1,
+                          shared1: bool = False) -> dict[str, np.ndarray]:
+    """The reference's ``data`` dict for ``SuperGlue.forward`` (superglue.py:264-284) as float32
+    numpy: descriptors0/1 [B,256,n], keypoints0/1 [B,n,2], scores0/1 [B,n], image0/1 (only their
+    shape is read: 512 x 512).  Image 1's points are another view of image 0's (``_sg_derive``).
+    With ``shared1`` image 1 is one set for the whole batch (made from sample 0's image 0; the
+    other samples' image 0 are views of it) and is returned with batch dimension 1."""
+    rs = np.random.RandomState(seed)
+    kp0, d0, kp1, d1 = [], [], [], []
+    for b in range(batch):
+        if shared1 and b > 0:
+            k, d = _sg_derive(rs, kp1[0], d1[0], n0)
+        else:
+            k = rs.uniform(0, SUPERGLUE_IMAGE, size=(n0, 2))
+            d = _unit_rows(rs.standard_normal((n0, DESC_DIM)))
+        kp0.append(k)
+        d0.append(d)
+        if not (shared1 and b > 0):
+            k1, dd1 = _sg_derive(rs, k, d, n1)
+            kp1.append(k1)
+            d1.append(dd1)
+    b1 = len(kp1)
+    f32 = np.float32
+    return {
+        "descriptors0": np.ascontiguousarray(np.stack(d0).transpose(0, 2, 1)).astype(f32),
+        "descriptors1": np.ascontiguousarray(np.stack(d1).transpose(0, 2, 1)).astype(f32),
+        "keypoints0": np.stack(kp0).astype(f32),
+        "keypoints1": np.stack(kp1).astype(f32),
+        "scores0": rs.uniform(0.01, 1.0, size=(batch, n0)).astype(f32),
+        "scores1": rs.uniform(0.01, 1.0, size=(b1, n1)).astype(f32),
+        "image0": np.zeros((batch, 1, SUPERGLUE_IMAGE, SUPERGLUE_IMAGE), f32),
+        "image1": np.zeros((b1, 1, SUPERGLUE_IMAGE, SUPERGLUE_IMAGE), f32),
+    }
