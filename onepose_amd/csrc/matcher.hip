@@ -26,17 +26,13 @@
 // Steps 3-5 are an exact re-association of message = merge(attention), MLP(cat[x, msg])
 // (the linear attention output and the merge conv are linear in the message): the fp32
 // result differs from the reference's evaluation order only in rounding.
-#include <cmath>
-#include <cstdarg>
-#include <cstring>
-#include <vector>
-
-#include "gemm.h"
-
 #include <algorithm>
-#include <atomic>
+#include <cmath>
 #include <mutex>
 #include <unordered_map>
+
+#include "gemm.h"
+#include "matcher_pack.h"
 
 namespace onepose {
 
@@ -80,191 +76,6 @@ __device__ unsigned g_device_errors;
 __global__ void cache_hdr_kernel(unsigned* hdr, CacheHdr h) {
   if (threadIdx.x < kCacheHdrWords) hdr[threadIdx.x] = (&h.magic)[threadIdx.x];
 }
-
-// ------------------------------------------------------------------------------------
-// errors
-// ------------------------------------------------------------------------------------
-static thread_local std::string g_last_error;
-
-void set_error(const char* fmt, ...) {
-  char buf[1024];
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(buf, sizeof(buf), fmt, ap);
-  va_end(ap);
-  g_last_error = buf;
-}
-void clear_error() { g_last_error.clear(); }
-
-// ------------------------------------------------------------------------------------
-// launch profiling
-// ------------------------------------------------------------------------------------
-namespace {
-struct Prof {
-  uint64_t mask = 0;
-  bool device = false;   // device-stamp mode
-  std::vector<hipEvent_t> ev;
-  std::vector<int> kinds;
-  int n = 0;
-  StampAcc* acc[K_NUM_KINDS] = {};   // device, kStampPool sites, allocated per stamped kind
-  int next[K_NUM_KINDS] = {};   // round-robin pool cursor per kind
-};
-// Each launch (or graph node captured while stamping) gets its own accumulator from the
-// kind's pool, so launches of one kind that run concurrently (several match streams)
-// never share one; a graph node keeps its accumulator across replays, which of the same
-// graph are serialised.
-// Launch sites per kind: a graph node keeps its site; eager launches cycle through the pool,
-// and 120 is a multiple of the per-frame launch counts (8 mlp1, 12 SuperPoint convs), so a
-// site always sees the same grid (the ticket -> launch arithmetic divides by its wave count).
-constexpr int kStampPool = 120;
-Prof g_prof;
-const char* kKindNames[K_NUM_KINDS] = {
-    "transpose_in", "gat", "qkv_gemm", "kv_reduce", "m_fold", "mlp1_gemm",
-    "stats_finalize", "mlp2_gemm", "final_gemm", "l2norm", "score_gemm", "softmax_reduce",
-    "conf", "mutual", "select", "pnp_ransac", "pnp_refit", "pose_error", "sample_desc",
-    "sp_conv", "sp_nms", "sp_select", "sp_desc", "sg_input", "sg_attention", "sg_sinkhorn",
-    "sg_match"};
-}  // namespace
-
-StampAcc* prof_stamp_slot(int kind) {
-  if (!g_prof.device || !((g_prof.mask >> kind) & 1ull) || g_prof.acc[kind] == nullptr)
-    return nullptr;
-  const int i = g_prof.next[kind]++ % kStampPool;
-  return g_prof.acc[kind] + i;
-}
-
-void prof_pre(int kind, hipStream_t s) {
-  if (g_prof.device) return;
-  if (!((g_prof.mask >> kind) & 1ull) || 2 * g_prof.n + 1 >= (int)g_prof.ev.size()) return;
-  (void)hipEventRecord(g_prof.ev[2 * g_prof.n], s);
-}
-void prof_post(int kind, hipStream_t s) {
-  if (g_prof.device) return;
-  if (!((g_prof.mask >> kind) & 1ull) || 2 * g_prof.n + 1 >= (int)g_prof.ev.size()) return;
-  (void)hipEventRecord(g_prof.ev[2 * g_prof.n + 1], s);
-  g_prof.kinds[g_prof.n] = kind;
-  ++g_prof.n;
-}
-
-// ------------------------------------------------------------------------------------
-// weight packing (host)
-// ------------------------------------------------------------------------------------
-namespace {
-
-constexpr int kLayers = 12;
-constexpr int kApLayers = 8;
-constexpr int kGatLayers = 4;
-
-// packed panel, floats (per attention layer):
-//   Wqkv [768][256]: rows 0..255 q head-major (packed row h*64+d <- reference row d*4+h),
-//                    then per head h: 64 rows of k_h, 64 rows of v_h
-//   bqkv [768]
-//   W1a [512][256] = mlp.0.weight[:, :256]
-//   C   [512][256] = mlp.0.weight[:, 256:] @ merge.weight, columns head-major (h*64+q)
-//   b1f [512]      = mlp.0.bias + mlp.0.weight[:, 256:] @ merge.bias
-//   W2 [256][512], b2 [256]
-//   CT [4][64][512]: CT[h][q][o] = C[o][h*64+q]  (the fold's operand, o contiguous)
-constexpr int64_t kApWqkv = 768 * 256, kApBqkv = 768;
-constexpr int64_t kApW1a = 512 * 256, kApC = 512 * 256, kApB1 = 512, kApW2 = 256 * 512,
-                  kApB2 = 256, kApCT = 512 * 256;
-constexpr int64_t kApFloats = kApWqkv + kApBqkv + kApW1a + kApC + kApB1 + kApW2 + kApB2 + kApCT;
-constexpr int64_t kGatFloats = 512;
-constexpr int64_t kFinalFloats = 256 * 256 + 256;
-constexpr int64_t kPackedFloats = kApLayers * kApFloats + kGatLayers * kGatFloats + kFinalFloats;
-// ... then, per attention layer, the bf16 planes of its three weight matrices for the bf16
-// modes (gemm.h GemmProb::Wp): Wqkv, W1a and W2 split exactly into hi / mid / lo
-// (hi = bf16(x) rounded to nearest even: PM_BF16's operand), [3][rows][cols] uint16 each.
-constexpr int64_t kPlWqkv = 768 * 256, kPlW1a = 512 * 256, kPlW2 = 256 * 512;
-constexpr int64_t kApPlanes = 3 * (kPlWqkv + kPlW1a + kPlW2);   // uint16 per layer
-constexpr int64_t kPackedBytes = kPackedFloats * 4 + kApLayers * kApPlanes * 2;
-
-struct ApW {
-  const float *wqkv, *bqkv, *w1a, *c, *b1, *w2, *b2, *ct;
-  const uint16_t *wqkv_p, *w1a_p, *w2_p;   // bf16 planes
-};
-ApW ap_weights(const float* base, int ap) {
-  const float* p = base + (int64_t)ap * kApFloats;
-  ApW w;
-  const uint16_t* pl = reinterpret_cast<const uint16_t*>(base + kPackedFloats) + (int64_t)ap * kApPlanes;
-  w.wqkv_p = pl;
-  w.w1a_p = pl + 3 * kPlWqkv;
-  w.w2_p = w.w1a_p + 3 * kPlW1a;
-  w.wqkv = p; p += kApWqkv;
-  w.bqkv = p; p += kApBqkv;
-  w.w1a = p; p += kApW1a;
-  w.c = p; p += kApC;
-  w.b1 = p; p += kApB1;
-  w.w2 = p; p += kApW2;
-  w.b2 = p; p += kApB2;
-  w.ct = p;
-  return w;
-}
-
-// bf16 bits of x rounded to nearest even (the device's (__bf16)x for finite x)
-uint16_t bf16_rne(float x) {
-  uint32_t u;
-  memcpy(&u, &x, 4);
-  u += 0x7fffu + ((u >> 16) & 1u);
-  return (uint16_t)(u >> 16);
-}
-float bf16_val(uint16_t b) {
-  const uint32_t u = (uint32_t)b << 16;
-  float f;
-  memcpy(&f, &u, 4);
-  return f;
-}
-// the exact split x = hi + mid + lo of gemm.hip's store_quad_bf16, into planes n elements apart
-void split_planes(const float* x, int64_t n, uint16_t* out) {
-  for (int64_t i = 0; i < n; ++i) {
-    const uint16_t h = bf16_rne(x[i]);
-    const float r = x[i] - bf16_val(h);
-    const uint16_t m = bf16_rne(r);
-    out[i] = h;
-    out[n + i] = m;
-    out[2 * n + i] = bf16_rne(r - bf16_val(m));
-  }
-}
-const float* gat_weights(const float* base, int g) {
-  return base + kApLayers * kApFloats + (int64_t)g * kGatFloats;
-}
-const float* final_weights(const float* base) {
-  return base + kApLayers * kApFloats + kGatLayers * kGatFloats;
-}
-
-struct TensorSpec {
-  std::string name;
-  int64_t numel;
-};
-
-const std::vector<TensorSpec>& tensor_specs() {
-  static std::vector<TensorSpec> specs = [] {
-    std::vector<TensorSpec> s;
-    for (int i = 0; i < kLayers; ++i) {
-      std::string p = "gnn.layers." + std::to_string(i) + ".";
-      if (i % 3 == 0) {
-        s.push_back({p + "W", 256 * 256});
-        s.push_back({p + "a", 512});
-      } else {
-        for (int j = 0; j < 3; ++j) {
-          s.push_back({p + "attn.proj." + std::to_string(j) + ".weight", 256 * 256});
-          s.push_back({p + "attn.proj." + std::to_string(j) + ".bias", 256});
-        }
-        s.push_back({p + "attn.merge.weight", 256 * 256});
-        s.push_back({p + "attn.merge.bias", 256});
-        s.push_back({p + "mlp.0.weight", 512 * 512});
-        s.push_back({p + "mlp.0.bias", 512});
-        s.push_back({p + "mlp.3.weight", 256 * 512});
-        s.push_back({p + "mlp.3.bias", 256});
-      }
-    }
-    s.push_back({"final_proj.weight", 256 * 256});
-    s.push_back({"final_proj.bias", 256});
-    return s;
-  }();
-  return specs;
-}
-
-}  // namespace
 
 // ------------------------------------------------------------------------------------
 // kernels
@@ -1486,7 +1297,7 @@ bool valid_precision(int p) {
 // `planes`: carve the bf16 modes' activation planes (kPlanesMax per tensor); fp32 never reads
 // them (match_impl's pl() is null there), so an fp32 plan leaves them out (+75% of
 // the per-token footprint otherwise).
-Plan make_plan(void* ws, int B, int n1, int n3, int L, bool with_conf, bool planes = true) {
+Plan make_plan(void* ws, int B, int n1, int n3, int L, bool with_conf, bool planes) {
   Carve c(ws);
   Plan p;
   const size_t t2 = (size_t)B * n1, t3 = (size_t)B * n3;
@@ -1551,230 +1362,11 @@ using namespace onepose;
 
 extern "C" {
 
-const char* onepose_last_error(void) { return g_last_error.c_str(); }
-int onepose_abi_version(void) { return 8; }
-
-int onepose_profile_begin(uint64_t kind_mask, int capacity) {
-  clear_error();
-  OP_REQUIRE(capacity >= 0, "profile: capacity %d", capacity);
-  const size_t need = 2 * (size_t)capacity + 2;
-  while (g_prof.ev.size() < need) {
-    hipEvent_t e;
-    OP_HIP(hipEventCreate(&e));
-    g_prof.ev.push_back(e);
-  }
-  g_prof.kinds.assign(capacity + 1, -1);
-  g_prof.n = 0;
-  g_prof.mask = kind_mask;
-  g_prof.device = false;
-  return ONEPOSE_OK;
-}
-
-int onepose_profile_begin_device(uint64_t kind_mask) {
-  clear_error();
-  // per stamped kind: allocated once (graph nodes keep their sites' addresses), zeroed on
-  // every call (all zero = armed)
-  OP_HIP(hipDeviceSynchronize());
-  for (int k = 0; k < K_NUM_KINDS; ++k) {
-    if (!((kind_mask >> k) & 1ull)) continue;
-    if (g_prof.acc[k] == nullptr)
-      OP_HIP(hipMalloc(&g_prof.acc[k], sizeof(StampAcc) * kStampPool));
-    OP_HIP(hipMemset(g_prof.acc[k], 0, sizeof(StampAcc) * kStampPool));
-  }
-  OP_HIP(hipDeviceSynchronize());
-  g_prof.n = 0;
-  g_prof.mask = kind_mask;
-  g_prof.device = true;
-  return ONEPOSE_OK;
-}
-
-int onepose_profile_end_device(int64_t* launches, double* total_ms, int n_kinds) {
-  clear_error();
-  OP_REQUIRE(g_prof.device, "profile_end_device: device stamping not active");
-  g_prof.device = false;
-  const uint64_t mask = g_prof.mask;
-  g_prof.mask = 0;
-  OP_HIP(hipDeviceSynchronize());
-  std::vector<unsigned long long> tot(K_NUM_KINDS, 0ull), cnt(K_NUM_KINDS, 0ull);
-  std::vector<StampAcc> pool(kStampPool);
-  for (int k = 0; k < K_NUM_KINDS; ++k) {
-    if (!((mask >> k) & 1ull) || g_prof.acc[k] == nullptr) continue;
-    OP_HIP(hipMemcpy(pool.data(), g_prof.acc[k], sizeof(StampAcc) * kStampPool,
-                     hipMemcpyDeviceToHost));
-    for (const StampAcc& s : pool)   // launches past kStampRecs per site (s.overflow) dropped
-      for (int e = 0; e < kStampRecs; ++e) {
-        unsigned long long st = ~0ull, en = 0ull;
-        for (int j = 0; j < kStampShards; ++j) {
-          const StampRec& r = s.rec[e][j];
-          if (r.end == 0) continue;
-          st = std::min(st, ~r.nstart);
-          en = std::max(en, r.end);
-        }
-        if (en == 0) continue;
-        tot[k] += en > st ? en - st : 0ull;
-        ++cnt[k];
-      }
-  }
-  int dev = 0, khz = 0;
-  OP_HIP(hipGetDevice(&dev));
-  OP_HIP(hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, dev));
-  OP_REQUIRE(khz > 0, "profile: wall clock rate unavailable");
-  for (int k = 0; k < n_kinds; ++k) {
-    const bool ok = k < K_NUM_KINDS;
-    if (launches) launches[k] = ok ? (int64_t)cnt[k] : 0;
-    if (total_ms) total_ms[k] = ok ? (double)tot[k] / khz : 0.0;
-  }
-  return ONEPOSE_OK;
-}
-
-int onepose_profile_end(int* kinds, float* ms, int capacity, int* count) {
-  clear_error();
-  g_prof.mask = 0;
-  const int n = g_prof.n;
-  if (count) *count = n;
-  if (n > 0) OP_HIP(hipEventSynchronize(g_prof.ev[2 * n - 1]));
-  for (int i = 0; i < n && i < capacity; ++i) {
-    float t = 0.f;
-    OP_HIP(hipEventElapsedTime(&t, g_prof.ev[2 * i], g_prof.ev[2 * i + 1]));
-    if (ms) ms[i] = t;
-    if (kinds) kinds[i] = g_prof.kinds[i];
-  }
-  g_prof.n = 0;
-  return ONEPOSE_OK;
-}
-
-const char* onepose_profile_kind_name(int kind) {
-  return (kind >= 0 && kind < K_NUM_KINDS) ? kKindNames[kind] : nullptr;
-}
-
-int onepose_matcher_num_tensors(void) { return (int)tensor_specs().size(); }
-
-const char* onepose_matcher_tensor_name(int i) {
-  const auto& s = tensor_specs();
-  if (i < 0 || i >= (int)s.size()) return nullptr;
-  return s[i].name.c_str();
-}
-
-int64_t onepose_matcher_tensor_numel(int i) {
-  const auto& s = tensor_specs();
-  if (i < 0 || i >= (int)s.size()) return -1;
-  return s[i].numel;
-}
-
-size_t onepose_matcher_packed_bytes(void) { return (size_t)kPackedBytes; }
-
-int onepose_matcher_pack(const float* const* tensors, int n_tensors, void* packed_host) {
-  clear_error();
-  const auto& specs = tensor_specs();
-  OP_REQUIRE(tensors != nullptr && packed_host != nullptr, "pack: null pointer");
-  OP_REQUIRE(n_tensors == (int)specs.size(), "pack: expected %d tensors, got %d",
-             (int)specs.size(), n_tensors);
-  for (int i = 0; i < n_tensors; ++i) OP_REQUIRE(tensors[i] != nullptr, "pack: tensor %d null", i);
-  float* out = static_cast<float*>(packed_host);
-  int ti = 0, ap = 0, gat = 0;
-  for (int layer = 0; layer < kLayers; ++layer) {
-    if (layer % 3 == 0) {
-      const float* W = tensors[ti++];   // [256 in][256 out]
-      const float* a = tensors[ti++];   // [512]
-      float* wa = out + kApLayers * kApFloats + (int64_t)gat * kGatFloats;
-      for (int c = 0; c < 256; ++c) {
-        double lo = 0.0, hi = 0.0;
-        for (int j = 0; j < 256; ++j) {
-          lo += (double)W[c * 256 + j] * (double)a[j];
-          hi += (double)W[c * 256 + j] * (double)a[256 + j];
-        }
-        wa[c] = (float)lo;
-        wa[256 + c] = (float)hi;
-      }
-      ++gat;
-      continue;
-    }
-    float* p = out + (int64_t)ap * kApFloats;
-    float* wq = p;
-    float* wkv = wq + 256 * 256;
-    float* bq = p + kApWqkv;
-    float* bkv = bq + 256;
-    float* w1a = bq + kApBqkv;
-    float* cw = w1a + kApW1a;
-    float* b1 = cw + kApC;
-    float* w2 = b1 + kApB1;
-    float* b2 = w2 + kApW2;
-    const float* pw[3];
-    const float* pb[3];
-    for (int j = 0; j < 3; ++j) {
-      pw[j] = tensors[ti++];
-      pb[j] = tensors[ti++];
-    }
-    const float* mw = tensors[ti++];   // merge [256][256]
-    const float* mb = tensors[ti++];
-    const float* m0w = tensors[ti++];  // mlp.0 [512][512]
-    const float* m0b = tensors[ti++];
-    const float* m3w = tensors[ti++];  // mlp.3 [256][512]
-    const float* m3b = tensors[ti++];
-    // q: packed row h*64+d <- reference row d*4+h (view(B, 64, 4, N), :116)
-    for (int cp = 0; cp < 256; ++cp) {
-      const int h = cp / 64, d = cp % 64, cr = d * 4 + h;
-      memcpy(wq + (int64_t)cp * 256, pw[0] + (int64_t)cr * 256, 256 * sizeof(float));
-      bq[cp] = pb[0][cr];
-    }
-    // k / v interleaved per head: rows [128h, 128h+64) = k_h, [128h+64, 128h+128) = v_h
-    for (int h = 0; h < 4; ++h)
-      for (int d = 0; d < 64; ++d) {
-        const int cr = d * 4 + h;
-        memcpy(wkv + (int64_t)(128 * h + d) * 256, pw[1] + (int64_t)cr * 256, 256 * sizeof(float));
-        memcpy(wkv + (int64_t)(128 * h + 64 + d) * 256, pw[2] + (int64_t)cr * 256,
-               256 * sizeof(float));
-        bkv[128 * h + d] = pb[1][cr];
-        bkv[128 * h + 64 + d] = pb[2][cr];
-      }
-    // MLP conv 1 split: x part as is; message part folded with the merge conv.  Each output is
-    // one double chain over j in ascending order; the merge weight is read through a
-    // transposed double copy (packed column order) and eight chains run side by side, so the
-    // fold is not bound by strided loads and one dependent chain (1.09 -> 0.19 s per model on
-    // this container's CPU; the same chains, the same bits).
-    std::vector<double> mwt((size_t)256 * 256);   // [cp][j] = merge[j][cr(cp)]
-    for (int cp = 0; cp < 256; ++cp) {   // merge input channel q*4+h -> packed h*64+q
-      const int h = cp / 64, q = cp % 64, cr = q * 4 + h;
-      for (int j = 0; j < 256; ++j) mwt[(size_t)cp * 256 + j] = (double)mw[(int64_t)j * 256 + cr];
-    }
-    for (int o = 0; o < 512; ++o) {
-      memcpy(w1a + (int64_t)o * 256, m0w + (int64_t)o * 512, 256 * sizeof(float));
-      const float* mo = m0w + (int64_t)o * 512 + 256;
-      double bacc = (double)m0b[o];
-      for (int j = 0; j < 256; ++j) bacc += (double)mo[j] * mb[j];
-      b1[o] = (float)bacc;
-      double arow[256];
-      for (int j = 0; j < 256; ++j) arow[j] = (double)mo[j];
-      for (int cp0 = 0; cp0 < 256; cp0 += 8) {
-        double acc[8] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-        const double* wt = mwt.data() + (size_t)cp0 * 256;
-        for (int j = 0; j < 256; ++j)
-          for (int k = 0; k < 8; ++k) acc[k] += arow[j] * wt[(size_t)k * 256 + j];
-        for (int k = 0; k < 8; ++k) cw[(int64_t)o * 256 + cp0 + k] = (float)acc[k];
-      }
-    }
-    memcpy(w2, m3w, kApW2 * sizeof(float));
-    memcpy(b2, m3b, kApB2 * sizeof(float));
-    float* ct = b2 + kApB2;
-    for (int o = 0; o < 512; ++o)
-      for (int cp = 0; cp < 256; ++cp) ct[(int64_t)cp * 512 + o] = cw[(int64_t)o * 256 + cp];
-    uint16_t* pl = reinterpret_cast<uint16_t*>(out + kPackedFloats) + (int64_t)ap * kApPlanes;
-    split_planes(wq, kPlWqkv, pl);   // wq: the whole [768][256] panel (q rows, then k_h / v_h)
-    split_planes(w1a, kPlW1a, pl + 3 * kPlWqkv);
-    split_planes(w2, kPlW2, pl + 3 * (kPlWqkv + kPlW1a));
-    ++ap;
-  }
-  float* fin = out + kApLayers * kApFloats + kGatLayers * kGatFloats;
-  memcpy(fin, tensors[ti++], 256 * 256 * sizeof(float));
-  memcpy(fin + 256 * 256, tensors[ti++], 256 * sizeof(float));
-  return ONEPOSE_OK;
-}
-
 size_t onepose_match_workspace_bytes(int batch, int n1, int n3, int num_leaf, int with_conf) {
   clear_error();
   if (batch <= 0 || n1 <= 0 || n3 <= 0) return 0;
   OP_REQUIRE(num_leaf >= 1 && num_leaf <= 16, "workspace: num_leaf=%d", num_leaf);
-  return make_plan(nullptr, batch, n1, n3, num_leaf, with_conf != 0).bytes;   // every precision
+  return make_plan(nullptr, batch, n1, n3, num_leaf, with_conf != 0, true).bytes;   // every precision
 }
 
 size_t onepose_match_workspace_bytes_ex(int batch, int n1, int n3, int num_leaf, int with_conf,
@@ -1785,10 +1377,6 @@ size_t onepose_match_workspace_bytes_ex(int batch, int n1, int n3, int num_leaf,
   return make_plan(nullptr, batch, n1, n3, num_leaf, with_conf != 0,
                    precision != ONEPOSE_PREC_FP32).bytes;
 }
-
-}  // extern "C"
-
-extern "C" {
 
 }  // extern "C"
 
@@ -1994,9 +1582,8 @@ struct SideCache {
   const uint16_t* phiqp;   // [3][n3][256] phi(q)'s activation planes (bf16 modes)
 };
 
-void launch_kv_fold(const KvFoldArgs& ka, int nslot, int B, float* kv, float* ksum, hipStream_t st) {
-  hipLaunchKernelGGL(kv_fold256_kernel, dim3(nslot * B * (64 * KVF_OSPLIT + 1)), dim3(256), 0, st, ka, kv, ksum, B);
-}
+// kv_fold256_kernel's grid over `nslot` source slots of a batch
+dim3 kv_fold_grid(int nslot, int B) { return dim3(nslot * B * (64 * KVF_OSPLIT + 1)); }
 
 // AttentionPropagation (GATs_SuperGlue.py:123-132) for 1 or 2 sides, grouped into one launch
 // per step wherever the sides' choices (LayerTiles) agree.  Each side's arithmetic is
@@ -2007,7 +1594,7 @@ void launch_kv_fold(const KvFoldArgs& ka, int nslot, int B, float* kv, float* ks
 // starts the 3D side from its cached accumulators.
 int attention_layer(const ApW& w, const Side* sd, int nside, int B, const Plan& p,
                     unsigned* cnt, hipStream_t st, int pm, const ShardCtx* sh,
-                    const LayerTiles& tl, const SideCache* xc = nullptr) {
+                    const LayerTiles& tl, const SideCache* xc) {
   int rc;
   OP_REQUIRE(!xc || (nside == 2 && !sh), "attention layer: cached cross half");
   OP_REQUIRE(!sh || (!tl.fused_fold[0] && !tl.fused_fold[1] && tl.qkv[0] == tl.qkv[1]),
@@ -2078,10 +1665,8 @@ int attention_layer(const ApW& w, const Side* sd, int nside, int B, const Plan& 
         ka.p[i - i0] = {sd[i].kvpart, sd[i].kspart, chunks(i)};
         ka.mf[i - i0] = mf_of(reader[i]);
       }
-      prof_pre(K_KV_REDUCE, st);
-      launch_kv_fold(ka, ns, B, kv, ksum, st);
-      prof_post(K_KV_REDUCE, st);
-      OP_LAUNCHED();
+      OP_LAUNCH(K_KV_REDUCE, st, kv_fold256_kernel, kv_fold_grid(ns, B), dim3(256), 0, st, ka, kv,
+                ksum, B);
       return (int)ONEPOSE_OK;
     }
     KvArgs kva;
@@ -2234,35 +1819,174 @@ struct StateSlots {
   }
 };
 
-// The matcher forward on point-major leaves [*, n3*L, 256] (leaves_pm_bs elements per sample).
-// obj_cache (onepose_match_cached): the 3D side entering layer 2, [n3][256] shared by the
-// batch (onepose_object_prepare) -- GAT 0 and the 3D half of self-attention 1 are skipped.
-// desc_dt (ONEPOSE_DT_*): the element type of desc2d and of an uncached desc3d.
-int match_impl(const void* packed_weights, const void* desc2d, int64_t desc2d_bstride,
-               const void* desc3d, int64_t desc3d_bstride, const float* leaves_pm,
-               int64_t leaves_pm_bs, int batch, int n1, int n3, int num_leaf, float scale_factor,
-               float match_threshold, int64_t* matches0, int64_t* matches1, float* mscores0,
-               float* mscores1, float* conf, const Plan& p, hipStream_t st, int precision,
-               const ShardCtx* sh = nullptr, const float* obj_cache = nullptr,
-               int obj_flags = 0, int desc_dt = ONEPOSE_DT_F32,
-               const CacheHdr* obj_hdr = nullptr, int first_stage = ONEPOSE_STAGE_INPUTS,
-               int last_stage = ONEPOSE_STAGE_WINNERS) {
+// One matcher forward as its entry point describes it (host only, never passed to a kernel).
+// The 3D side is the uncached descriptors desc3d (element type desc_dt, as desc2d), this rank's
+// columns of them (shard), or the object cache (obj_cache, which desc3d then names too: the 3D
+// side entering layer 2, [n3][256] shared by the batch -- GAT 0 and the 3D half of
+// self-attention 1 are skipped).
+struct MatchCall {
+  const void* weights = nullptr;
+  const void* desc2d = nullptr;
+  int64_t desc2d_bs = 0;
+  int desc_dt = ONEPOSE_DT_F32;
+  const void* desc3d = nullptr;
+  int64_t desc3d_bs = 0;
+  const float* leaves_pm = nullptr;   // point-major leaves [*, n3*L, 256]
+  int64_t leaves_pm_bs = 0;           //   elements per sample (0: one object for the batch)
+  int batch = 0, n1 = 0, n3 = 0, num_leaf = 0;
+  float scale_factor = 0.f, match_threshold = 0.f;
+  int precision = ONEPOSE_PREC_FP32;
+  int64_t *matches0 = nullptr, *matches1 = nullptr;
+  float *mscores0 = nullptr, *mscores1 = nullptr, *conf = nullptr;
+  hipStream_t stream = nullptr;
+  const ShardCtx* shard = nullptr;
+  const float* obj_cache = nullptr;
+  int obj_flags = 0;
+  bool has_obj_hdr = false;   // obj_hdr: what the cache's device header must say (checked_plan)
+  CacheHdr obj_hdr{};
   // the stages [first_stage, last_stage] of the forward (onepose_match_cached_stages)
-  auto in_range = [&](int stage) { return stage >= first_stage && stage <= last_stage; };
-  const bool with_conf = conf != nullptr;
-  const int n3g = sh ? sh->n3_total : n3;   // the 3D side's full length (softmax / attention)
-  const int pm = attention_pm(precision);   // attention-layer GEMM operand mode
-  const int pm_out = precision == ONEPOSE_PREC_FP32_SPLIT ? PM_SPLIT3 : PM_F32;   // final, score
-  const float* wbase = static_cast<const float*>(packed_weights);
-  const int B = batch;
-  float* S = with_conf ? conf : p.s;
-  const float* leaves = leaves_pm;
-  const int64_t leaves_bstride = leaves_pm_bs;
+  int first_stage = ONEPOSE_STAGE_INPUTS, last_stage = ONEPOSE_STAGE_WINNERS;
+};
 
+// What onepose_object_prepare built into each cache, keyed by the cache's device address. The
+// cache's layout depends on (n3, num_leaf, flags) and its Mf region's format on the precision
+// (fp32, or bf16 planes), and the device copy cannot be read back without a synchronisation,
+// which a graph-captured launch must not do. So the host records them at prepare time and
+// onepose_match_cached refuses a cache whose record is missing or differs from its arguments.
+struct CacheRecord {
+  int n3, num_leaf, precision, flags;
+  unsigned long long gen;   // also in the cache's device header (CacheHdr)
+};
+std::mutex g_cache_mu;
+std::unordered_map<const void*, CacheRecord> g_caches;
+unsigned long long g_cache_gen = 0;
+
+// `leaves`: the leaves as the caller passed them (onepose_match_dt: not yet point-major)
+int check_match_args(const MatchCall& c, const void* leaves, const void* workspace) {
+  OP_REQUIRE(c.weights && c.desc2d && c.desc3d && leaves, "match: null input");
+  OP_REQUIRE(c.matches0 && c.matches1 && c.mscores0 && c.mscores1, "match: null output");
+  OP_REQUIRE(c.batch >= 1 && c.n1 >= 1 && c.n3 >= 1, "match: batch=%d n1=%d n3=%d", c.batch, c.n1,
+             c.n3);
+  OP_REQUIRE(c.num_leaf >= 1 && c.num_leaf <= 16, "match: num_leaf=%d not in [1,16]", c.num_leaf);
+  OP_REQUIRE(c.scale_factor != 0.f, "match: scale_factor 0");
+  OP_REQUIRE(workspace != nullptr, "match: null workspace");
+  return ONEPOSE_OK;
+}
+
+// a plan (and `tail` bytes behind it) against the caller's workspace
+int plan_fits(const char* who, const Plan& p, size_t tail, size_t ws_bytes) {
+  if (ws_bytes < p.bytes + tail) {
+    set_error("%s: workspace %zu < %zu bytes", who, ws_bytes, p.bytes + tail);
+    return ONEPOSE_ERR_WORKSPACE;
+  }
+  return ONEPOSE_OK;
+}
+
+// The part of a match entry point's checks that all of them share, and the plan.  Each entry
+// point first makes the refusals that are its own (stages, precision, dtype, flags, the shard's
+// geometry) in its own order; then, in the one order that serves them all: the common arguments,
+// a cached call's object cache against the registry (-> c->obj_hdr), a sharded call's exchange
+// buffers, the workspace size.  The plan is made once, on the real base (Carve's offsets and
+// `bytes` do not depend on it).
+int checked_plan(const char* who, MatchCall* c, const void* leaves, void* ws, size_t ws_bytes,
+                 Plan* out) {
+  int rc = check_match_args(*c, leaves, ws);
+  if (rc != ONEPOSE_OK) return rc;
+  if (c->obj_cache != nullptr) {
+    std::lock_guard<std::mutex> lk(g_cache_mu);
+    const auto it = g_caches.find(c->obj_cache);
+    OP_REQUIRE(it != g_caches.end(),
+               "match_cached: object_cache was not built by onepose_object_prepare (or was "
+               "released)");
+    const CacheRecord& r = it->second;
+    OP_REQUIRE(r.n3 == c->n3 && r.num_leaf == c->num_leaf && r.precision == c->precision &&
+                   r.flags == c->obj_flags,
+               "match_cached: cache prepared for n3=%d num_leaf=%d precision=%d flags=%d, "
+               "called with n3=%d num_leaf=%d precision=%d flags=%d",
+               r.n3, r.num_leaf, r.precision, r.flags, c->n3, c->num_leaf, c->precision,
+               c->obj_flags);
+    c->obj_hdr = cache_hdr(r.n3, r.num_leaf, r.precision, r.flags, r.gen);
+    c->has_obj_hdr = true;
+  }
+  size_t tail = 0;   // a sharded call's column winners of the whole frame, behind the plan
+  if (const ShardCtx* sh = c->shard) {
+    const size_t need_x = shard_xchg_bytes(c->batch, c->n1, sh->n3_total, sh->world);
+    if (sh->cap < need_x) {
+      set_error("match_sharded: exchange buffers %zu < %zu bytes per rank", sh->cap, need_x);
+      return ONEPOSE_ERR_WORKSPACE;
+    }
+    tail = align_up((size_t)c->batch * sh->n3_total * 8, 256);
+  }
+  // planes = true when sharded: the sharded workspace size (an ABI-visible query) has always
+  // included the activation planes, in every precision
+  const bool planes = c->shard != nullptr || c->precision != ONEPOSE_PREC_FP32;
+  *out = make_plan(ws, c->batch, c->n1, c->n3, c->num_leaf, c->conf != nullptr, planes);
+  return plan_fits(who, *out, tail, ws_bytes);
+}
+
+// transpose_in: `n` tokens of a [*][256][n] input (bs elements per sample) -> token-major dst
+// (+ its activation planes dstp); run = false: a problem without workgroups
+TransProb trans_prob(const void* src, int64_t bs, int n, bool f16, bool run, float* dst,
+                     uint16_t* dstp) {
+  TransProb t = {src, bs, n, run ? ceil_div(n, 64) * 4 : 0, dst, dstp};
+  t.f16 = f16 ? 1 : 0;
+  return t;
+}
+// ... its arguments for two problems, zeroing `nzero` arrival counters
+TransArgs transpose_args(const TransProb& a, const TransProb& b, unsigned* zero, int nzero) {
+  return TransArgs{{a, b}, zero, nzero};
+}
+int launch_transpose(const TransArgs& ta, int B, hipStream_t st) {
+  OP_LAUNCH(K_TRANSPOSE, st, transpose_in_kernel, dim3((ta.p[0].tiles + ta.p[1].tiles) * B),
+            dim3(256), 0, st, ta, B);
+  return ONEPOSE_OK;
+}
+
+// One GAT layer (packed vectors wa) on B samples of n3 points: x3 -> y3 and its activation
+// planes y3p.  The leaf logits are computed from the leaves, or read from slog (an object
+// cache's stored logits); with tab_logits / tab (the cache's prefix tables, num_leaf <= 8) the
+// leaves are not read at all.
+// (Defined below match_impl, beside its other user: templates are instantiated in the order of
+// their first use, and there the GAT kernels keep their place in the code object.)
+int launch_gat(const float* x3, const float* leaves, int64_t leaves_bs, const float* wa,
+               const float* slog, const float* tab_logits, const float* tab, float* y3,
+               uint16_t* y3p, int npl, int n3, int num_leaf, int B, hipStream_t st);
+
+// Side `which` (0: 2D, 1: 3D) of an attention layer on the plan's per-layer scratch: the state
+// x (batch stride x_bs) and its planes xp in, xo and its planes xop out (the planes only in
+// the bf16 modes, npl != 0).
+Side make_side(const Plan& p, int which, int npl, const float* x, int64_t x_bs,
+               const uint16_t* xp, float* xo, uint16_t* xop, int n, float len, int src,
+               int ntile) {
+  Side s = which == 0 ? Side{x, x_bs, xo, p.phiq2, p.kvpart2, p.kspart2, p.y12, p.stats2, n, len,
+                             src, ntile}
+                      : Side{x, x_bs, xo, p.phiq3, p.kvpart3, p.kspart3, p.y13, p.stats3, n, len,
+                             src, ntile};
+  s.xp = xp;
+  s.xp_bs = (int64_t)kPlanesMax * n * 256;
+  s.xop = npl ? xop : nullptr;
+  s.phiqp = npl ? (which == 0 ? p.phiq2p : p.phiq3p) : nullptr;
+  return s;
+}
+
+// A forward in flight: what the call and the plan fix for all its stages, and where the two
+// sides' states are.  Side x is read from x?r (batch stride x3bs for the 3D side) and written to
+// p.x?[sl.c? ^ 1]; their activation planes (bf16 modes) are read from x?pr (null: the object
+// cache's state, which only cached halves read).
+struct Forward {
+  const MatchCall& c;
+  const Plan& p;
+  Forward(const MatchCall& call, const Plan& plan) : c(call), p(plan) {}
+  uint16_t* pl(uint16_t* q) const { return npl ? q : nullptr; }
+
+  const float* wbase = static_cast<const float*>(c.weights);
+  const int pm = attention_pm(c.precision);   // attention-layer GEMM operand mode
+  const int pm_out = c.precision == ONEPOSE_PREC_FP32_SPLIT ? PM_SPLIT3 : PM_F32;   // final, score
   // bf16 modes: every producer of an attention GEMM's A operand also writes its activation
   // planes (the token states x2 / x3, phi(q)), which those GEMMs then move by DMA
   const int npl = planes_of(pm);
-  auto pl = [&](uint16_t* q) { return npl ? q : nullptr; };
+  const int n3g = c.shard ? c.shard->n3_total : c.n3;   // the 3D side's full length
+  const int score_mt = ceil_div(c.n1, pm_out == PM_F32 ? kScoreBM : 64);   // colpart per column
   // the dual softmax's statistics inside conf_kernel (whole frames, few score M-tiles, at most
   // kConfRowTiles score tiles per row): no softmax_reduce launch; the packed column winners are
   // zeroed by the first kernel instead.  Every conf workgroup re-derives its rows' statistics
@@ -2270,235 +1994,269 @@ int match_impl(const void* packed_weights, const void* desc2d, int64_t desc2d_bs
   // re-reads (n3 / 256 times each) cost more than the separate softmax_reduce launch: config 5
   // conf 55.7 -> 36.4 + 7.6 us, config 3 1.91 -> 0.76 ms per step, the same bits
   // (profiles/r05/conf_rpl/, profiles/r05/smx/)
-  const int score_mt = ceil_div(n1, pm_out == PM_F32 ? kScoreBM : 64);   // colpart per column
-  const bool conf_stats = !sh && score_mt <= kConfColTiles && ceil_div(n3, 64) <= kConfRowTiles;
-  // the dual softmax's winners and the mutual check (ONEPOSE_STAGE_WINNERS): the score GEMM's
-  // partials and S in the workspace -> matches / scores
-  auto winners = [&]() -> int {
-    int rc;
-    const int ch3 = ceil_div(n3, 64);
-    const int64_t total = (int64_t)B * (n1 + n3);
-    if (!conf_stats)
-      OP_LAUNCH(K_SMX_REDUCE, st, softmax_reduce_kernel, dim3((unsigned)((total + 3) / 4)),
-                dim3(256), 0, st, p.rowpart, ch3, p.colpart, score_mt, B, n1, n3, p.rowmax,
-                p.rowsum, p.colmax, p.colsum, p.rowbest, p.colbest);
-    const int64_t nr = (int64_t)B * n1;
-    if (sh) {   // row softmax over every rank's columns
-      OP_HIP(hipMemcpyAsync(sh->send, p.rowmax, nr * 4, hipMemcpyDeviceToDevice, st));
-      OP_HIP(hipMemcpyAsync(sh->send + nr * 4, p.rowsum, nr * 4, hipMemcpyDeviceToDevice, st));
-      if ((rc = shard_exchange(*sh, nr * 8, st)) != ONEPOSE_OK) return rc;
-      OP_LAUNCH(K_SMX_REDUCE, st, rowstat_merge_kernel, dim3((unsigned)((nr + 255) / 256)),
-                dim3(256), 0, st, reinterpret_cast<const float*>(sh->recv), sh->world, 2 * nr, nr,
-                p.rowmax, p.rowsum);
+  const bool conf_stats =
+      !c.shard && score_mt <= kConfColTiles && ceil_div(c.n3, 64) <= kConfRowTiles;
+  const ObjLayout obj = obj_layout(c.n3, c.num_leaf, c.obj_flags, npl != 0);   // (cached forwards)
+  float* const S = c.conf ? c.conf : p.s;   // the score / conf matrix
+  StateSlots sl{c.obj_cache != nullptr};
+  int ap = 0, gat = 0;   // attention / GAT layers passed
+  const float* x2r = p.x2[0];
+  const float* x3r = c.obj_cache ? c.obj_cache : p.x3[0];
+  int64_t x3bs = c.obj_cache ? 0 : (int64_t)c.n3 * 256;
+  const uint16_t* x2pr = pl(p.x2p[0]);
+  const uint16_t* x3pr = c.obj_cache ? nullptr : pl(p.x3p[0]);
+};
+
+// ONEPOSE_STAGE_INPUTS: both inputs token-major (a cached forward: the 2D side only), the
+// forward's counters zeroed and its object cache's header checked
+int stage_inputs(Forward& f) {
+  const MatchCall& c = f.c;
+  const Plan& p = f.p;
+  const bool f16 = c.desc_dt == ONEPOSE_DT_F16, cached = c.obj_cache != nullptr;
+  TransArgs ta = transpose_args(
+      trans_prob(c.desc2d, c.desc2d_bs, c.n1, f16, true, p.x2[0], f.pl(p.x2p[0])),
+      trans_prob(c.desc3d, c.desc3d_bs, c.n3, !cached && f16, !cached, p.x3[0], f.pl(p.x3p[0])),
+      p.cnt, p.ncnt);
+  ta.npl = f.npl;
+  if (f.conf_stats) {
+    ta.zero64 = p.colbest;
+    ta.nzero64 = (int64_t)c.batch * c.n3;
+  }
+  ta.err = p.err;
+  if (cached && c.has_obj_hdr) {
+    ta.hdr = reinterpret_cast<const unsigned*>(c.obj_cache + f.obj.hdr);
+    ta.expect = c.obj_hdr;
+  }
+  return launch_transpose(ta, c.batch, c.stream);
+}
+
+// A GAT layer: updates the 3D side only (GAT 0 of a cached forward: nothing at all).
+// run = false (here and in attention_stage): the layer ran in an earlier call on the same
+// workspace, or runs in a later one -- only track which buffers hold the states.
+int gat_layer(Forward& f, int layer, bool run) {
+  const MatchCall& c = f.c;
+  const Plan& p = f.p;
+  const bool cached = c.obj_cache != nullptr;
+  if (!StateSlots::from_cache(cached, layer)) {
+    const int64_t g1 = (int64_t)(f.gat - 1) * c.n3;   // points of GAT layers 1 .. gat - 1
+    // the object's stored leaf logits (one object for the whole batch: leaves stride 0)
+    const bool stored = cached && c.leaves_pm_bs == 0 && f.gat >= 1;
+    const bool tables = stored && f.obj.tables;
+    uint16_t* yp = f.pl(p.x3p[f.sl.c3 ^ 1]);
+    if (run) {
+      const int rc = launch_gat(
+          f.x3r, c.leaves_pm, c.leaves_pm_bs, gat_weights(f.wbase, f.gat),
+          stored ? c.obj_cache + f.obj.logits + g1 * kLogitStride : nullptr,
+          tables ? c.obj_cache + f.obj.slogs + g1 * kLogitStride : nullptr,
+          tables ? c.obj_cache + f.obj.tab + g1 * 2 * c.num_leaf * 256 : nullptr,
+          p.x3[f.sl.c3 ^ 1], yp, f.npl, c.n3, c.num_leaf, c.batch, c.stream);
+      if (rc != ONEPOSE_OK) return rc;
     }
-    const int coff = sh ? sh->offset : 0;
-    const dim3 cgrid(ceil_div(n1, 32) * ceil_div(n3, 256), B);
+    f.x3pr = yp;
+  }
+  f.sl.after(layer, cached);
+  if (!f.sl.x3_cached) f.x3r = p.x3[f.sl.c3];
+  ++f.gat;
+  return ONEPOSE_OK;
+}
+
+// A 'self' (each side attends to itself) or 'cross' (2D <-> 3D) layer on both sides
+int attention_stage(Forward& f, int layer, bool run) {
+  const MatchCall& c = f.c;
+  const Plan& p = f.p;
+  const ShardCtx* sh = c.shard;
+  const int B = c.batch, n1 = c.n1, n3 = c.n3;
+  const bool cross = layer % 3 == 2, cached = c.obj_cache != nullptr;
+  const bool cached3 = StateSlots::from_cache(cached, layer);   // the 3D side comes from the cache
+  const int c2 = f.sl.c2, c3 = f.sl.c3;   // the buffers holding the states entering this layer
+  const int a = f.ap++;
+  const ApW w = ap_weights(f.wbase, a);
+  const int ntile3 = sh ? sh->max_shard : n3;
+  const Side sd[2] = {
+      make_side(p, 0, f.npl, f.x2r, (int64_t)n1 * 256, f.x2pr, p.x2[c2 ^ 1], p.x2p[c2 ^ 1], n1,
+                (float)n1, cross ? 1 : 0, n1),
+      make_side(p, 1, f.npl, f.x3r, f.x3bs, f.x3pr, p.x3[c3 ^ 1], p.x3p[c3 ^ 1], n3,
+                (float)f.n3g, cross ? 0 : 1, ntile3)};
+  unsigned* lcnt = p.cnt + (size_t)a * 2 * B * p.cps;
+  // layers 1-2 of a whole frame: per-side choices (the 3D side's are the object prefix's,
+  // so cached and uncached forwards agree bit for bit at any batch); later layers and
+  // sharded frames: one set for the launch
+  const LayerTiles tl = !sh && a < 2 ? side_tiles(n1, n3, B, f.pm, cross)
+                                     : layer_tiles(ntile3, sd, 2, B, f.pm, sh != nullptr);
+  int rc = ONEPOSE_OK;
+  if (!run) {
+  } else if (cached3) {   // self-attention 1, 2D half (the 3D half is in the object cache)
+    rc = attention_layer(w, sd, 1, B, p, lcnt, c.stream, f.pm, sh, tl, nullptr);
+  } else if (cached && layer == 2 && !sh) {
+    // cross-attention 1: the 3D side's frame-independent half from the object cache
+    const ObjLayout& L = f.obj;
+    const SideCache xc = {c.obj_cache + L.phiq, c.obj_cache + L.acc, c.obj_cache + L.ksum,
+                          c.obj_cache + L.mf,
+                          f.npl ? reinterpret_cast<const uint16_t*>(c.obj_cache + L.phiqp) : nullptr};
+    rc = attention_layer(w, sd, 2, B, p, lcnt, c.stream, f.pm, nullptr, tl, &xc);
+  } else {
+    rc = attention_layer(w, sd, 2, B, p, lcnt, c.stream, f.pm, sh, tl, nullptr);
+  }
+  if (rc != ONEPOSE_OK) return rc;
+  f.sl.after(layer, cached);
+  f.x2r = p.x2[f.sl.c2];
+  f.x2pr = sd[0].xop;
+  if (!cached3) {
+    f.x3r = p.x3[f.sl.c3];
+    f.x3pr = sd[1].xop;
+    f.x3bs = (int64_t)n3 * 256;
+  }
+  return ONEPOSE_OK;
+}
+
+// ONEPOSE_STAGE_FINAL: final_proj on both sides, then L2 normalise
+int stage_final(Forward& f) {
+  const MatchCall& c = f.c;
+  const Plan& p = f.p;
+  const int B = c.batch, n1 = c.n1, n3 = c.n3;
+  hipStream_t st = c.stream;
+  const float* fw = final_weights(f.wbase);
+  GemmArgs a;
+  a.nprob = 2;
+  a.p[0] = gemm_prob(f.x2r, 256, fw, 256, fw + 65536, p.f2, 256, n1, 256, 256, B);
+  a.p[1] = gemm_prob(f.x3r, 256, fw, 256, fw + 65536, p.f3, 256, n3, 256, 256, B);
+  // fp32: whole-row tiles normalise in the epilogue (l2norm_kernel's arithmetic, the same
+  // bits), one launch and one pass over f2 / f3 fewer; half the workgroups of 64 x 64,
+  // which leaves CUs to the other match stream
+  if (f.pm_out == PM_F32)
+    return gemm_launch(EPI_BIAS_L2, PRO_PLAIN, kTileFinalL2, a, st, K_FINAL, f.pm_out);
+  const int rc = gemm_launch(EPI_BIAS, PRO_PLAIN, kTileFinal, a, st, K_FINAL, f.pm_out);
+  if (rc != ONEPOSE_OK) return rc;
+  const int rows = B * (n1 + n3);
+  OP_LAUNCH(K_L2NORM, st, l2norm_kernel, dim3(ceil_div(rows, 4)), dim3(256), 0, st, p.f2, B * n1,
+            p.f3, B * n3);
+  return ONEPOSE_OK;
+}
+
+// ONEPOSE_STAGE_SCORE: S = D2^T D3 / scale_factor with softmax partials
+int stage_score(Forward& f) {
+  const MatchCall& c = f.c;
+  const Plan& p = f.p;
+  // score tile: 128 x 64 on 8 waves in fp32 (K = 256 is short; fewer operand loads per FLOP
+  // than 64 x 64), 64 x 64 in the split mode (its LDS images are three bf16 planes)
+  const int score_tile = f.pm_out == PM_F32 ? kTileScore : TILE_64x64;
+  GemmArgs a;
+  a.nprob = 1;
+  a.p[0] = gemm_prob(p.f2, 256, p.f3, 256, nullptr, f.S, c.n3, c.n1, c.n3, 256, c.batch);
+  a.p[0].w_bs = (int64_t)c.n3 * 256;
+  a.p[0].scale = c.scale_factor;
+  a.p[0].rowstat = p.rowpart;
+  a.p[0].colstat = p.colpart;
+  return gemm_launch(EPI_SCORE, PRO_PLAIN, score_tile, a, c.stream, K_SCORE, f.pm_out);
+}
+
+// ONEPOSE_STAGE_WINNERS: the dual softmax's winners and the mutual check -- the score GEMM's
+// partials and S in the workspace -> matches / scores
+int stage_winners(Forward& f) {
+  const MatchCall& c = f.c;
+  const Plan& p = f.p;
+  const ShardCtx* sh = c.shard;
+  const int B = c.batch, n1 = c.n1, n3 = c.n3, n3g = f.n3g, score_mt = f.score_mt;
+  hipStream_t st = c.stream;
+  const bool with_conf = c.conf != nullptr;
+  float* S = f.S;
+  int rc;
+  const int ch3 = ceil_div(n3, 64);
+  const int64_t total = (int64_t)B * (n1 + n3);
+  if (!f.conf_stats)
+    OP_LAUNCH(K_SMX_REDUCE, st, softmax_reduce_kernel, dim3((unsigned)((total + 3) / 4)),
+              dim3(256), 0, st, p.rowpart, ch3, p.colpart, score_mt, B, n1, n3, p.rowmax,
+              p.rowsum, p.colmax, p.colsum, p.rowbest, p.colbest);
+  const int64_t nr = (int64_t)B * n1;
+  if (sh) {   // row softmax over every rank's columns
+    OP_HIP(hipMemcpyAsync(sh->send, p.rowmax, nr * 4, hipMemcpyDeviceToDevice, st));
+    OP_HIP(hipMemcpyAsync(sh->send + nr * 4, p.rowsum, nr * 4, hipMemcpyDeviceToDevice, st));
+    if ((rc = shard_exchange(*sh, nr * 8, st)) != ONEPOSE_OK) return rc;
+    OP_LAUNCH(K_SMX_REDUCE, st, rowstat_merge_kernel, dim3((unsigned)((nr + 255) / 256)),
+              dim3(256), 0, st, reinterpret_cast<const float*>(sh->recv), sh->world, 2 * nr, nr,
+              p.rowmax, p.rowsum);
+  }
+  const int coff = sh ? sh->offset : 0;
+  const dim3 cgrid(ceil_div(n1, 32) * ceil_div(n3, 256), B);
 #define CONF_LAUNCH(V, ST)                                                                   \
   OP_LAUNCH(K_CONF, st, (conf_kernel<V, ST>), cgrid, dim3(kConfWaves * 64), 0, st, S, n1, n3,  \
             p.rowmax,                                                                       \
             p.rowsum, p.colmax, p.colsum, p.rowwin, p.colbest, with_conf ? 1 : 0, coff,     \
             p.rowpart, ch3, p.colpart, score_mt)
-    if (n3 % 4 == 0) {
-      if (conf_stats) CONF_LAUNCH(true, true);
-      else CONF_LAUNCH(true, false);
-    } else {
-      if (conf_stats) CONF_LAUNCH(false, true);
-      else CONF_LAUNCH(false, false);
-    }
+  if (n3 % 4 == 0) {
+    if (f.conf_stats) CONF_LAUNCH(true, true);
+    else CONF_LAUNCH(true, false);
+  } else {
+    if (f.conf_stats) CONF_LAUNCH(false, true);
+    else CONF_LAUNCH(false, false);
+  }
 #undef CONF_LAUNCH
-    const unsigned long long* colbest = p.colbest;
-    const unsigned long long* rowwin = p.rowwin;
-    if (sh) {   // row winners over all columns; every rank's column winners at global columns
-      OP_LAUNCH(K_MUTUAL, st, rowbest_reduce_kernel, dim3((unsigned)((nr + 255) / 256)), dim3(256),
-                0, st, p.rowwin, ceil_div(n3, 256), nr,
-                reinterpret_cast<unsigned long long*>(sh->send));
-      rowwin = nullptr;
-      if ((rc = shard_exchange(*sh, nr * 8, st)) != ONEPOSE_OK) return rc;
-      OP_LAUNCH(K_MUTUAL, st, best_max_kernel, dim3((unsigned)((nr + 255) / 256)), dim3(256), 0, st,
-                reinterpret_cast<const unsigned long long*>(sh->recv), sh->world, nr, nr,
-                p.rowbest);
-      const int64_t nc = (int64_t)B * sh->max_shard;
-      OP_LAUNCH(K_MUTUAL, st, colbest_pack_kernel, dim3((unsigned)((nc + 255) / 256)), dim3(256), 0,
-                st, p.colbest, B, n3, sh->max_shard,
-                reinterpret_cast<unsigned long long*>(sh->send));
-      if ((rc = shard_exchange(*sh, nc * 8, st)) != ONEPOSE_OK) return rc;
-      const int64_t nf = (int64_t)B * n3g;
-      OP_LAUNCH(K_MUTUAL, st, colbest_assemble_kernel, dim3((unsigned)((nf + 255) / 256)),
-                dim3(256), 0, st, reinterpret_cast<const unsigned long long*>(sh->recv), sh->world,
-                nc, B, n3g, sh->max_shard, sh->colbest_full);
-      colbest = sh->colbest_full;
-    }
-    const int64_t tot_g = (int64_t)B * (n1 + n3g);
-    OP_LAUNCH(K_MUTUAL, st, mutual_kernel, dim3((unsigned)((tot_g + 255) / 256)), dim3(256), 0, st,
-                       p.rowbest, rowwin, ceil_div(n3, 256), colbest, B, n1, n3g,
-                       match_threshold, matches0, matches1,
-                       mscores0, mscores1, p.err);
-    return ONEPOSE_OK;
-  };
-  {
-    TransArgs ta;
-    ta.p[0] = {desc2d, desc2d_bstride, n1, ceil_div(n1, 64) * 4, p.x2[0], pl(p.x2p[0])};
-    ta.p[1] = {desc3d, desc3d_bstride, n3, obj_cache ? 0 : ceil_div(n3, 64) * 4, p.x3[0],
-               pl(p.x3p[0])};
-    ta.p[0].f16 = desc_dt == ONEPOSE_DT_F16;
-    ta.p[1].f16 = !obj_cache && desc_dt == ONEPOSE_DT_F16;
-    ta.zero = p.cnt;
-    ta.nzero = p.ncnt;
-    ta.npl = npl;
-    if (conf_stats) {
-      ta.zero64 = p.colbest;
-      ta.nzero64 = (int64_t)B * n3;
-    }
-    ta.err = p.err;
-    if (obj_cache != nullptr && obj_hdr != nullptr) {
-      ta.hdr = reinterpret_cast<const unsigned*>(
-          obj_cache + obj_layout(n3, num_leaf, obj_flags, npl != 0).hdr);
-      ta.expect = *obj_hdr;
-    }
-    if (in_range(ONEPOSE_STAGE_INPUTS))
-      OP_LAUNCH(K_TRANSPOSE, st, transpose_in_kernel, dim3((ta.p[0].tiles + ta.p[1].tiles) * B),
-                dim3(256), 0, st, ta, B);
+  const unsigned long long* colbest = p.colbest;
+  const unsigned long long* rowwin = p.rowwin;
+  if (sh) {   // row winners over all columns; every rank's column winners at global columns
+    OP_LAUNCH(K_MUTUAL, st, rowbest_reduce_kernel, dim3((unsigned)((nr + 255) / 256)), dim3(256),
+              0, st, p.rowwin, ceil_div(n3, 256), nr,
+              reinterpret_cast<unsigned long long*>(sh->send));
+    rowwin = nullptr;
+    if ((rc = shard_exchange(*sh, nr * 8, st)) != ONEPOSE_OK) return rc;
+    OP_LAUNCH(K_MUTUAL, st, best_max_kernel, dim3((unsigned)((nr + 255) / 256)), dim3(256), 0, st,
+              reinterpret_cast<const unsigned long long*>(sh->recv), sh->world, nr, nr,
+              p.rowbest);
+    const int64_t nc = (int64_t)B * sh->max_shard;
+    OP_LAUNCH(K_MUTUAL, st, colbest_pack_kernel, dim3((unsigned)((nc + 255) / 256)), dim3(256), 0,
+              st, p.colbest, B, n3, sh->max_shard,
+              reinterpret_cast<unsigned long long*>(sh->send));
+    if ((rc = shard_exchange(*sh, nc * 8, st)) != ONEPOSE_OK) return rc;
+    const int64_t nf = (int64_t)B * n3g;
+    OP_LAUNCH(K_MUTUAL, st, colbest_assemble_kernel, dim3((unsigned)((nf + 255) / 256)),
+              dim3(256), 0, st, reinterpret_cast<const unsigned long long*>(sh->recv), sh->world,
+              nc, B, n3g, sh->max_shard, sh->colbest_full);
+    colbest = sh->colbest_full;
   }
-  if (last_stage < ONEPOSE_STAGE_LAYER0 || first_stage > ONEPOSE_STAGE_SCORE)
-    return in_range(ONEPOSE_STAGE_WINNERS) ? winners() : ONEPOSE_OK;
+  const int64_t tot_g = (int64_t)B * (n1 + n3g);
+  OP_LAUNCH(K_MUTUAL, st, mutual_kernel, dim3((unsigned)((tot_g + 255) / 256)), dim3(256), 0, st,
+            p.rowbest, rowwin, ceil_div(n3, 256), colbest, B, n1, n3g, c.match_threshold,
+            c.matches0, c.matches1, c.mscores0, c.mscores1, p.err);
+  return ONEPOSE_OK;
+}
 
-  // Current states: side x is read from x?r (batch stride x?bs) and written to p.x?[c? ^ 1];
-  // their activation planes (bf16 modes) from x?pr (null: the object cache's state, which only
-  // cached halves read)
-  StateSlots sl(obj_cache != nullptr);
-  int ap = 0, gat = 0;
-  const float* x2r = p.x2[0];
-  const float* x3r = obj_cache ? obj_cache : p.x3[0];
-  int64_t x3bs = obj_cache ? 0 : (int64_t)n3 * 256;
-  const uint16_t* x2pr = pl(p.x2p[0]);
-  const uint16_t* x3pr = obj_cache ? nullptr : pl(p.x3p[0]);
-  for (int layer = 0; layer < kLayers; ++layer) {
-    if (last_stage < ONEPOSE_STAGE_LAYER0 + layer) return ONEPOSE_OK;
-    // a layer outside the range ran in an earlier call on the same workspace (or runs in a
-    // later one): the loop only tracks which buffers hold the states
-    const bool run_layers = in_range(ONEPOSE_STAGE_LAYER0 + layer);
-    const int kind = layer % 3;  // 0 GATs, 1 self, 2 cross
-    // the 3D side comes from the cache
-    const bool cached3 = StateSlots::from_cache(obj_cache != nullptr, layer);
-    const int c2 = sl.c2, c3 = sl.c3;   // the buffers holding the states entering this layer
-    if (kind == 0) {
-      if (!cached3) {
-        const dim3 ggrid(ceil_div(B * n3, 4));
-        // the object's stored leaf logits (one object for the whole batch: leaves stride 0)
-        const float* slog = obj_cache && leaves_bstride == 0 && gat >= 1
-                                ? obj_cache + (int64_t)n3 * 256 +
-                                      (int64_t)(gat - 1) * n3 * kLogitStride
-                                : nullptr;
-        const ObjLayout OL = obj_layout(n3, num_leaf, obj_flags, npl != 0);
-        uint16_t* yp = pl(p.x3p[c3 ^ 1]);
-        if (!run_layers) {
-        } else if (slog != nullptr && OL.tables) {
-          OP_LAUNCH(K_GAT, st, gat_tab_kernel, ggrid, dim3(256), 0, st, x3r, gat_weights(wbase, gat),
-                    obj_cache + OL.slogs + (int64_t)(gat - 1) * n3 * kLogitStride,
-                    obj_cache + OL.tab + (int64_t)(gat - 1) * n3 * 2 * num_leaf * 256,
-                    p.x3[c3 ^ 1], n3, num_leaf, B, yp, npl);
-        } else if (num_leaf <= 8)
-          OP_LAUNCH(K_GAT, st, gat_kernel<8>, ggrid, dim3(256), 0, st, x3r, leaves,
-                    leaves_bstride, gat_weights(wbase, gat), slog, p.x3[c3 ^ 1], n3, num_leaf, B,
-                    yp, npl);
-        else
-          OP_LAUNCH(K_GAT, st, gat_kernel<16>, ggrid, dim3(256), 0, st, x3r, leaves,
-                    leaves_bstride, gat_weights(wbase, gat), slog, p.x3[c3 ^ 1], n3, num_leaf, B,
-                    yp, npl);
-        x3pr = yp;
-      }
-      sl.after(layer, obj_cache != nullptr);
-      if (!sl.x3_cached) x3r = p.x3[sl.c3];
-      ++gat;
-      continue;
-    }
-    const ApW w = ap_weights(wbase, ap++);
-    // self: each side attends to itself; cross: 2D <-> 3D
-    Side sd[2];
-    sd[0] = {x2r, (int64_t)n1 * 256, p.x2[c2 ^ 1], p.phiq2, p.kvpart2, p.kspart2, p.y12,
-             p.stats2, n1, (float)n1, kind == 1 ? 0 : 1, n1};
-    sd[1] = {x3r, x3bs, p.x3[c3 ^ 1], p.phiq3, p.kvpart3, p.kspart3, p.y13, p.stats3, n3,
-             (float)n3g, kind == 1 ? 1 : 0, sh ? sh->max_shard : n3};
-    const int64_t pbs2 = (int64_t)kPlanesMax * n1 * 256, pbs3 = (int64_t)kPlanesMax * n3 * 256;
-    sd[0].xp = x2pr;
-    sd[0].xp_bs = pbs2;
-    sd[0].xop = pl(p.x2p[c2 ^ 1]);
-    sd[0].phiqp = pl(p.phiq2p);
-    sd[1].xp = x3pr;
-    sd[1].xp_bs = pbs3;
-    sd[1].xop = pl(p.x3p[c3 ^ 1]);
-    sd[1].phiqp = pl(p.phiq3p);
-    const int qkv_n3 = sh ? sh->max_shard : n3;
-    unsigned* lcnt = p.cnt + (size_t)(ap - 1) * 2 * B * p.cps;
-    // layers 1-2 of a whole frame: per-side choices (the 3D side's are the object prefix's,
-    // so cached and uncached forwards agree bit for bit at any batch); later layers and
-    // sharded frames: one set for the launch
-    const LayerTiles tl = !sh && ap <= 2 ? side_tiles(n1, n3, B, pm, kind == 2)
-                                         : layer_tiles(qkv_n3, sd, 2, B, pm, sh);
-    int rc = ONEPOSE_OK;
-    if (!run_layers) {
-    } else if (cached3) {   // self-attention 1, 2D half (the 3D half is in the object cache)
-      rc = attention_layer(w, sd, 1, B, p, lcnt, st, pm, sh, tl);
-    } else if (obj_cache && layer == 2 && !sh) {
-      // cross-attention 1: the 3D side's frame-independent half from the object cache
-      const ObjLayout L = obj_layout(n3, num_leaf, obj_flags, npl != 0);
-      const SideCache xc = {obj_cache + L.phiq, obj_cache + L.acc, obj_cache + L.ksum,
-                            obj_cache + L.mf,
-                            npl ? reinterpret_cast<const uint16_t*>(obj_cache + L.phiqp) : nullptr};
-      rc = attention_layer(w, sd, 2, B, p, lcnt, st, pm, nullptr, tl, &xc);
-    } else {
-      rc = attention_layer(w, sd, 2, B, p, lcnt, st, pm, sh, tl);
-    }
-    if (rc != ONEPOSE_OK) return rc;
-    sl.after(layer, obj_cache != nullptr);
-    x2r = p.x2[sl.c2];
-    x2pr = sd[0].xop;
-    if (!cached3) {
-      x3r = p.x3[sl.c3];
-      x3pr = sd[1].xop;
-      x3bs = (int64_t)n3 * 256;
-    }
-  }
-
-  if (last_stage < ONEPOSE_STAGE_FINAL) return ONEPOSE_OK;
+// The matcher forward, stages [c.first_stage, c.last_stage] of the schedule in this file's
+// opening comment: inputs, the 12 layers (GAT, self, cross, ...), final projection, scores,
+// winners.  Layers outside the range only move the state bookkeeping.
+int match_impl(const MatchCall& c, const Plan& p) {
+  const auto in_range = [&](int stage) { return stage >= c.first_stage && stage <= c.last_stage; };
+  Forward f(c, p);
   int rc;
-  if (in_range(ONEPOSE_STAGE_FINAL)) {  // final_proj on both sides, then L2 normalise
-    const float* fw = final_weights(wbase);
-    GemmArgs a;
-    a.nprob = 2;
-    a.p[0] = gemm_prob(x2r, 256, fw, 256, fw + 65536, p.f2, 256, n1, 256, 256, B);
-    a.p[1] = gemm_prob(x3r, 256, fw, 256, fw + 65536, p.f3, 256, n3, 256, 256, B);
-    if (pm_out == PM_F32) {
-      // fp32: whole-row tiles normalise in the epilogue (l2norm_kernel's arithmetic, the same
-      // bits), one launch and one pass over f2 / f3 fewer; half the workgroups of 64 x 64,
-      // which leaves CUs to the other match stream
-      if ((rc = gemm_launch(EPI_BIAS_L2, PRO_PLAIN, kTileFinalL2, a, st, K_FINAL, pm_out)) !=
-          ONEPOSE_OK)
-        return rc;
-    } else {
-      if ((rc = gemm_launch(EPI_BIAS, PRO_PLAIN, kTileFinal, a, st, K_FINAL, pm_out)) != ONEPOSE_OK)
-        return rc;
-      const int rows = B * (n1 + n3);
-      OP_LAUNCH(K_L2NORM, st, l2norm_kernel, dim3(ceil_div(rows, 4)), dim3(256), 0, st, p.f2,
-                B * n1, p.f3, B * n3);
-    }
+  if (in_range(ONEPOSE_STAGE_INPUTS) && (rc = stage_inputs(f)) != ONEPOSE_OK) return rc;
+  if (c.last_stage < ONEPOSE_STAGE_LAYER0 || c.first_stage > ONEPOSE_STAGE_SCORE)
+    return in_range(ONEPOSE_STAGE_WINNERS) ? stage_winners(f) : ONEPOSE_OK;
+  for (int layer = 0; layer < kLayers; ++layer) {
+    if (c.last_stage < ONEPOSE_STAGE_LAYER0 + layer) return ONEPOSE_OK;
+    const bool run = in_range(ONEPOSE_STAGE_LAYER0 + layer);
+    rc = layer % 3 == 0 ? gat_layer(f, layer, run) : attention_stage(f, layer, run);
+    if (rc != ONEPOSE_OK) return rc;
   }
+  if (c.last_stage < ONEPOSE_STAGE_FINAL) return ONEPOSE_OK;
+  if (in_range(ONEPOSE_STAGE_FINAL) && (rc = stage_final(f)) != ONEPOSE_OK) return rc;
   if (!in_range(ONEPOSE_STAGE_SCORE)) return ONEPOSE_OK;   // (a range: no winners either)
-  // score tile: 128 x 64 on 8 waves in fp32 (K = 256 is short; fewer operand loads per FLOP
-  // than 64 x 64), 64 x 64 in the split mode (its LDS images are three bf16 planes)
-  const int score_tile = pm_out == PM_F32 ? kTileScore : TILE_64x64;
-  {  // S = D2^T D3 / scale_factor with softmax partials
-    GemmArgs a;
-    a.nprob = 1;
-    a.p[0] = gemm_prob(p.f2, 256, p.f3, 256, nullptr, S, n3, n1, n3, 256, B);
-    a.p[0].w_bs = (int64_t)n3 * 256;
-    a.p[0].scale = scale_factor;
-    a.p[0].rowstat = p.rowpart;
-    a.p[0].colstat = p.colpart;
-    if ((rc = gemm_launch(EPI_SCORE, PRO_PLAIN, score_tile, a, st, K_SCORE, pm_out)) != ONEPOSE_OK)
-      return rc;
-  }
-  return in_range(ONEPOSE_STAGE_WINNERS) ? winners() : ONEPOSE_OK;
+  if ((rc = stage_score(f)) != ONEPOSE_OK) return rc;
+  return in_range(ONEPOSE_STAGE_WINNERS) ? stage_winners(f) : ONEPOSE_OK;
+}
+
+int launch_gat(const float* x3, const float* leaves, int64_t leaves_bs, const float* wa,
+               const float* slog, const float* tab_logits, const float* tab, float* y3,
+               uint16_t* y3p, int npl, int n3, int num_leaf, int B, hipStream_t st) {
+  const dim3 grid(ceil_div(B * n3, 4));
+  if (tab != nullptr)
+    OP_LAUNCH(K_GAT, st, gat_tab_kernel, grid, dim3(256), 0, st, x3, wa, tab_logits, tab, y3, n3,
+              num_leaf, B, y3p, npl);
+  else if (num_leaf <= 8)
+    OP_LAUNCH(K_GAT, st, gat_kernel<8>, grid, dim3(256), 0, st, x3, leaves, leaves_bs, wa, slog,
+              y3, n3, num_leaf, B, y3p, npl);
+  else
+    OP_LAUNCH(K_GAT, st, gat_kernel<16>, grid, dim3(256), 0, st, x3, leaves, leaves_bs, wa, slog,
+              y3, n3, num_leaf, B, y3p, npl);
+  return ONEPOSE_OK;
 }
 
 // The frame-independent prefix of the 3D side (onepose_object_prepare): transpose, GAT 0
@@ -2511,53 +2269,41 @@ int object_prepare_impl(const void* packed_weights, const void* desc3d, int desc
                         float* cache, const Plan& p, hipStream_t st) {
   const float* wbase = static_cast<const float*>(packed_weights);
   const int pm = attention_pm(precision);
-  const int npl = planes_of(pm);   // activation planes (bf16 modes), as in match_impl
+  const int npl = planes_of(pm);   // activation planes (bf16 modes), as in a forward
   auto pl = [&](uint16_t* q) { return npl ? q : nullptr; };
-  {
-    TransArgs ta;
-    ta.p[0] = {desc3d, 0, n3, ceil_div(n3, 64) * 4, p.x3[0]};
-    ta.p[1] = {desc3d, 0, n3, 0, p.x3[0]};
-    ta.p[0].f16 = desc_dt == ONEPOSE_DT_F16;
-    ta.zero = p.cnt;
-    ta.nzero = p.ncnt;
-    OP_LAUNCH(K_TRANSPOSE, st, transpose_in_kernel, dim3(ta.p[0].tiles), dim3(256), 0, st, ta, 1);
-  }
+  const ObjLayout L = obj_layout(n3, num_leaf, flags, npl != 0);
+  int rc;
+  const TransArgs ta = transpose_args(
+      trans_prob(desc3d, 0, n3, desc_dt == ONEPOSE_DT_F16, true, p.x3[0], nullptr),
+      trans_prob(desc3d, 0, n3, false, false, p.x3[0], nullptr), p.cnt, p.ncnt);
+  if ((rc = launch_transpose(ta, 1, st)) != ONEPOSE_OK) return rc;
+  if ((rc = launch_gat(p.x3[0], leaves_pm, 0, gat_weights(wbase, 0), nullptr, nullptr, nullptr,
+                       p.x3[1], pl(p.x3p[1]), npl, n3, num_leaf, 1, st)) != ONEPOSE_OK)
+    return rc;
+  // leaf logits of GAT layers 1-3 (packed vectors from layer 1's on), and their prefix tables
   const dim3 ggrid(ceil_div(n3, 4));
-  const float* nolog = nullptr;
-  float* slog = cache + (int64_t)n3 * 256;   // leaf logits of GAT layers 1-3
-  if (num_leaf <= 8) {
-    OP_LAUNCH(K_GAT, st, gat_kernel<8>, ggrid, dim3(256), 0, st, p.x3[0], leaves_pm, (int64_t)0,
-              gat_weights(wbase, 0), nolog, p.x3[1], n3, num_leaf, 1, pl(p.x3p[1]), npl);
-    OP_LAUNCH(K_GAT, st, gat_logits_kernel<8>, ggrid, dim3(256), 0, st, leaves_pm,
-              gat_weights(wbase, 1), slog, n3, num_leaf);
-    const ObjLayout OL = obj_layout(n3, num_leaf, flags, npl != 0);
-    if (OL.tables)
-      OP_LAUNCH(K_GAT, st, gat_table_kernel, ggrid, dim3(256), 0, st, leaves_pm,
-                gat_weights(wbase, 1), cache + OL.slogs, cache + OL.tab, n3, num_leaf);
-  } else {
-    OP_LAUNCH(K_GAT, st, gat_kernel<16>, ggrid, dim3(256), 0, st, p.x3[0], leaves_pm, (int64_t)0,
-              gat_weights(wbase, 0), nolog, p.x3[1], n3, num_leaf, 1, pl(p.x3p[1]), npl);
-    OP_LAUNCH(K_GAT, st, gat_logits_kernel<16>, ggrid, dim3(256), 0, st, leaves_pm,
-              gat_weights(wbase, 1), slog, n3, num_leaf);
-  }
-  Side s3 = {p.x3[1], (int64_t)n3 * 256, cache, p.phiq3, p.kvpart3, p.kspart3, p.y13,
-             p.stats3, n3, (float)n3, 0, n3};
-  s3.xp = pl(p.x3p[1]);
-  s3.xp_bs = (int64_t)kPlanesMax * n3 * 256;
-  s3.xop = pl(p.x3p[0]);   // the cached state's planes: cross-attention 1's QKV below reads them
-  s3.phiqp = pl(p.phiq3p);
-  int rc = attention_layer(ap_weights(wbase, 0), &s3, 1, 1, p, p.cnt, st, pm, nullptr,
-                           layer_tiles(n3, &s3, 1, 1, pm, false));
+  const float* wa1 = gat_weights(wbase, 1);
+  if (num_leaf <= 8)
+    OP_LAUNCH(K_GAT, st, gat_logits_kernel<8>, ggrid, dim3(256), 0, st, leaves_pm, wa1,
+              cache + L.logits, n3, num_leaf);
+  else
+    OP_LAUNCH(K_GAT, st, gat_logits_kernel<16>, ggrid, dim3(256), 0, st, leaves_pm, wa1,
+              cache + L.logits, n3, num_leaf);
+  if (L.tables)
+    OP_LAUNCH(K_GAT, st, gat_table_kernel, ggrid, dim3(256), 0, st, leaves_pm, wa1,
+              cache + L.slogs, cache + L.tab, n3, num_leaf);
+  // (xop: the cached state's planes, which cross-attention 1's QKV below reads)
+  const Side s3 = make_side(p, 1, npl, p.x3[1], (int64_t)n3 * 256, pl(p.x3p[1]), cache, p.x3p[0],
+                            n3, (float)n3, 0, n3);
+  // (for cross-attention 1 below: = side_tiles' 3D choices)
+  const LayerTiles tl = layer_tiles(n3, &s3, 1, 1, pm, false);
+  rc = attention_layer(ap_weights(wbase, 0), &s3, 1, 1, p, p.cnt, st, pm, nullptr, tl, nullptr);
   if (rc != ONEPOSE_OK) return rc;
 
   // Cross-attention 1 (layer 2), the 3D side's frame-independent half, with the choices a
   // cached forward's layer 2 makes (batch <= kFusedFoldMaxBatch: QKV tile from n3 alone, one
   // kv_fold launch), so that its bits are the ones the uncached forward computes in place.
-  const ObjLayout L = obj_layout(n3, num_leaf, flags, npl != 0);
   const ApW w = ap_weights(wbase, 1);
-  const Side x3 = {cache, 0, nullptr, cache + L.phiq, p.kvpart3, p.kspart3, nullptr, nullptr, n3,
-                   (float)n3, 0, n3};
-  const LayerTiles tl = layer_tiles(n3, &x3, 1, 1, pm, false);   // = side_tiles' 3D choices
   {  // phi(q) into the cache; KV / sum phi(k) chunk partials
     GemmArgs a;
     a.nprob = 1;
@@ -2581,33 +2327,15 @@ int object_prepare_impl(const void* packed_weights, const void* desc3d, int desc
     ka.p[0] = {p.kvpart3, p.kspart3, ceil_div(n3, gemm_tile_stat_rows(tl.qkv[0]))};
     ka.mf[0] = cache + L.mf;
     ka.mf[1] = nullptr;
-    prof_pre(K_KV_REDUCE, st);
-    launch_kv_fold(ka, 1, 1, p.kv, cache + L.ksum, st);
-    prof_post(K_KV_REDUCE, st);
-    OP_LAUNCHED();
+    OP_LAUNCH(K_KV_REDUCE, st, kv_fold256_kernel, kv_fold_grid(1, 1), dim3(256), 0, st, ka, p.kv,
+              cache + L.ksum, 1);
   }
-  {  // MLP conv 1's x range: W1a x3 as raw accumulators of the TILE_64x64 MFMA sequence
-    GemmArgs a;
-    a.nprob = 1;
-    a.p[0] = gemm_prob(cache, 256, w.w1a, 256, nullptr, cache + L.acc, 512, n3, 512, 256, 1);
-    if (pm != PM_F32) set_w_planes(a.p[0], w.w1a_p, kPlW1a);
-    if ((rc = gemm_launch(EPI_ACC, PRO_PLAIN, mlp1_acc_tile(pm), a, st, K_MLP1, pm)) != ONEPOSE_OK)
-      return rc;
-  }
-  return ONEPOSE_OK;
-}
-
-int check_match_args(const void* packed_weights, const void* desc2d, const void* desc3d,
-                     const void* leaves, int batch, int n1, int n3, int num_leaf,
-                     float scale_factor, const int64_t* matches0, const int64_t* matches1,
-                     const float* mscores0, const float* mscores1, const void* workspace) {
-  OP_REQUIRE(packed_weights && desc2d && desc3d && leaves, "match: null input");
-  OP_REQUIRE(matches0 && matches1 && mscores0 && mscores1, "match: null output");
-  OP_REQUIRE(batch >= 1 && n1 >= 1 && n3 >= 1, "match: batch=%d n1=%d n3=%d", batch, n1, n3);
-  OP_REQUIRE(num_leaf >= 1 && num_leaf <= 16, "match: num_leaf=%d not in [1,16]", num_leaf);
-  OP_REQUIRE(scale_factor != 0.f, "match: scale_factor 0");
-  OP_REQUIRE(workspace != nullptr, "match: null workspace");
-  return ONEPOSE_OK;
+  // MLP conv 1's x range: W1a x3 as raw accumulators of the TILE_64x64 MFMA sequence
+  GemmArgs a;
+  a.nprob = 1;
+  a.p[0] = gemm_prob(cache, 256, w.w1a, 256, nullptr, cache + L.acc, 512, n3, 512, 256, 1);
+  if (pm != PM_F32) set_w_planes(a.p[0], w.w1a_p, kPlW1a);
+  return gemm_launch(EPI_ACC, PRO_PLAIN, mlp1_acc_tile(pm), a, st, K_MLP1, pm);
 }
 
 }  // namespace
@@ -2633,17 +2361,10 @@ int onepose_prepare_leaves_dt(const void* leaves, int dtype, int64_t leaves_bstr
   OP_REQUIRE(dtype == ONEPOSE_DT_F32 || dtype == ONEPOSE_DT_F16, "prepare_leaves: dtype %d", dtype);
   OP_REQUIRE(batch >= 1 && n3 >= 1 && num_leaf >= 1 && num_leaf <= 16,
              "prepare_leaves: batch=%d n3=%d num_leaf=%d", batch, n3, num_leaf);
-  hipStream_t st = static_cast<hipStream_t>(stream_);
-  const int ncol = n3 * num_leaf;
-  TransArgs ta;
-  ta.p[0] = {leaves, leaves_bstride, ncol, ceil_div(ncol, 64) * 4, out};
-  ta.p[1] = {leaves, 0, 1, 0, out};
-  ta.p[0].f16 = dtype == ONEPOSE_DT_F16;
-  ta.zero = nullptr;
-  ta.nzero = 0;
-  OP_LAUNCH(K_TRANSPOSE, st, transpose_in_kernel, dim3(ta.p[0].tiles * batch), dim3(256), 0, st,
-            ta, batch);
-  return ONEPOSE_OK;
+  const TransArgs ta = transpose_args(
+      trans_prob(leaves, leaves_bstride, n3 * num_leaf, dtype == ONEPOSE_DT_F16, true, out, nullptr),
+      trans_prob(leaves, 0, 1, false, false, out, nullptr), nullptr, 0);
+  return launch_transpose(ta, batch, static_cast<hipStream_t>(stream_));
 }
 
 int onepose_match_ex(const void* packed_weights, const float* desc2d, int64_t desc2d_bstride,
@@ -2669,27 +2390,25 @@ int onepose_match_dt(const void* packed_weights, const void* desc2d, int64_t des
              "match: precision %d", precision);
   OP_REQUIRE(desc_dtype == ONEPOSE_DT_F32 || desc_dtype == ONEPOSE_DT_F16, "match: dtype %d",
              desc_dtype);
-  int rc = check_match_args(packed_weights, desc2d, desc3d, leaves, batch, n1, n3, num_leaf,
-                            scale_factor, matches0, matches1, mscores0, mscores1, workspace);
+  MatchCall c;
+  c.weights = packed_weights; c.stream = static_cast<hipStream_t>(stream_);
+  c.desc2d = desc2d; c.desc2d_bs = desc2d_bstride; c.desc_dt = desc_dtype;
+  c.desc3d = desc3d; c.desc3d_bs = desc3d_bstride;
+  c.batch = batch; c.n1 = n1; c.n3 = n3; c.num_leaf = num_leaf;
+  c.scale_factor = scale_factor; c.match_threshold = match_threshold; c.precision = precision;
+  c.matches0 = matches0; c.matches1 = matches1; c.mscores0 = mscores0; c.mscores1 = mscores1;
+  c.conf = conf;
+  Plan p;
+  int rc = checked_plan("match", &c, leaves, workspace, workspace_bytes, &p);
   if (rc != ONEPOSE_OK) return rc;
-  const bool planes = precision != ONEPOSE_PREC_FP32;
-  const Plan need = make_plan(nullptr, batch, n1, n3, num_leaf, conf != nullptr, planes);
-  if (workspace_bytes < need.bytes) {
-    set_error("match: workspace %zu < %zu bytes", workspace_bytes, need.bytes);
-    return ONEPOSE_ERR_WORKSPACE;
-  }
-  hipStream_t st = static_cast<hipStream_t>(stream_);
-  const Plan p = make_plan(workspace, batch, n1, n3, num_leaf, conf != nullptr, planes);
   // reference layout [*, 256, n3*L] -> point-major copy in the workspace
   const int lb = leaves_bstride == 0 ? 1 : batch;
   if ((rc = onepose_prepare_leaves_dt(leaves, desc_dtype, leaves_bstride, lb, n3, num_leaf,
                                       p.leaves_pm, stream_)) != ONEPOSE_OK)
     return rc;
-  const int64_t pm_bs = leaves_bstride == 0 ? 0 : (int64_t)n3 * num_leaf * 256;
-  return match_impl(packed_weights, desc2d, desc2d_bstride, desc3d, desc3d_bstride, p.leaves_pm,
-                    pm_bs, batch, n1, n3, num_leaf, scale_factor, match_threshold, matches0,
-                    matches1, mscores0, mscores1, conf, p, st, precision, nullptr, nullptr, 0,
-                    desc_dtype);
+  c.leaves_pm = p.leaves_pm;
+  c.leaves_pm_bs = leaves_bstride == 0 ? 0 : (int64_t)n3 * num_leaf * 256;
+  return match_impl(c, p);
 }
 
 int onepose_match(const void* packed_weights, const float* desc2d, int64_t desc2d_bstride,
@@ -2714,21 +2433,18 @@ int onepose_match_prepared_ex(const void* packed_weights, const float* desc2d,
   clear_error();
   OP_REQUIRE(valid_precision(precision),
              "match: precision %d", precision);
-  int rc = check_match_args(packed_weights, desc2d, desc3d, leaves_prepared, batch, n1, n3,
-                            num_leaf, scale_factor, matches0, matches1, mscores0, mscores1,
-                            workspace);
-  if (rc != ONEPOSE_OK) return rc;
-  const bool planes = precision != ONEPOSE_PREC_FP32;
-  const Plan need = make_plan(nullptr, batch, n1, n3, num_leaf, conf != nullptr, planes);
-  if (workspace_bytes < need.bytes) {
-    set_error("match: workspace %zu < %zu bytes", workspace_bytes, need.bytes);
-    return ONEPOSE_ERR_WORKSPACE;
-  }
-  const Plan p = make_plan(workspace, batch, n1, n3, num_leaf, conf != nullptr, planes);
-  return match_impl(packed_weights, desc2d, desc2d_bstride, desc3d, desc3d_bstride,
-                    leaves_prepared, prepared_bstride, batch, n1, n3, num_leaf, scale_factor,
-                    match_threshold, matches0, matches1, mscores0, mscores1, conf, p,
-                    static_cast<hipStream_t>(stream_), precision);
+  MatchCall c;
+  c.weights = packed_weights; c.stream = static_cast<hipStream_t>(stream_);
+  c.desc2d = desc2d; c.desc2d_bs = desc2d_bstride;
+  c.desc3d = desc3d; c.desc3d_bs = desc3d_bstride;
+  c.leaves_pm = leaves_prepared; c.leaves_pm_bs = prepared_bstride;
+  c.batch = batch; c.n1 = n1; c.n3 = n3; c.num_leaf = num_leaf;
+  c.scale_factor = scale_factor; c.match_threshold = match_threshold; c.precision = precision;
+  c.matches0 = matches0; c.matches1 = matches1; c.mscores0 = mscores0; c.mscores1 = mscores1;
+  c.conf = conf;
+  Plan p;
+  const int rc = checked_plan("match", &c, leaves_prepared, workspace, workspace_bytes, &p);
+  return rc != ONEPOSE_OK ? rc : match_impl(c, p);
 }
 
 int onepose_match_prepared(const void* packed_weights, const float* desc2d,
@@ -2761,29 +2477,8 @@ size_t onepose_object_cache_bytes_ex(int n3, int num_leaf, int flags, int precis
 size_t onepose_object_prepare_workspace_bytes(int n3, int num_leaf) {
   clear_error();
   if (n3 <= 0 || num_leaf < 1 || num_leaf > 16) return 0;
-  return make_plan(nullptr, 1, 1, n3, num_leaf, false).bytes;
+  return make_plan(nullptr, 1, 1, n3, num_leaf, false, true).bytes;   // every precision
 }
-
-}  // extern "C"
-
-namespace onepose {
-namespace {
-// What onepose_object_prepare built into each cache, keyed by the cache's device address. The
-// cache's layout depends on (n3, num_leaf, flags) and its Mf region's format on the precision
-// (fp32, or bf16 planes), and the device copy cannot be read back without a synchronisation,
-// which a graph-captured launch must not do. So the host records them at prepare time and
-// onepose_match_cached refuses a cache whose record is missing or differs from its arguments.
-struct CacheRecord {
-  int n3, num_leaf, precision, flags;
-  unsigned long long gen;   // also in the cache's device header (CacheHdr)
-};
-std::mutex g_cache_mu;
-std::unordered_map<const void*, CacheRecord> g_caches;
-unsigned long long g_cache_gen = 0;
-}  // namespace
-}  // namespace onepose
-
-extern "C" {
 
 int onepose_object_prepare(const void* packed_weights, const float* desc3d,
                            const float* leaves_prepared, int n3, int num_leaf, int precision,
@@ -2808,19 +2503,16 @@ int onepose_object_prepare_dt(const void* packed_weights, const void* desc3d, in
              num_leaf);
   OP_REQUIRE((flags & ~ONEPOSE_OBJ_GAT_TABLES) == 0, "object_prepare: flags %d", flags);
   OP_REQUIRE(workspace != nullptr, "object_prepare: null workspace");
-  const size_t need = onepose_object_prepare_workspace_bytes(n3, num_leaf);
-  if (workspace_bytes < need) {
-    set_error("object_prepare: workspace %zu < %zu bytes", workspace_bytes, need);
-    return ONEPOSE_ERR_WORKSPACE;
-  }
-  const Plan p = make_plan(workspace, 1, 1, n3, num_leaf, false);
+  // (as onepose_object_prepare_workspace_bytes: with the planes, in every precision)
+  const Plan p = make_plan(workspace, 1, 1, n3, num_leaf, false, true);
+  int rc = plan_fits("object_prepare", p, 0, workspace_bytes);
+  if (rc != ONEPOSE_OK) return rc;
   {
     std::lock_guard<std::mutex> lk(g_cache_mu);
     g_caches.erase(cache);   // whatever it held before is gone from here on
   }
-  const int rc = object_prepare_impl(packed_weights, desc3d, desc_dtype, leaves_prepared, n3,
-                                     num_leaf, precision, flags, cache, p,
-                                     static_cast<hipStream_t>(stream_));
+  rc = object_prepare_impl(packed_weights, desc3d, desc_dtype, leaves_prepared, n3, num_leaf,
+                           precision, flags, cache, p, static_cast<hipStream_t>(stream_));
   if (rc != ONEPOSE_OK) return rc;
   unsigned long long gen;
   {
@@ -2893,37 +2585,20 @@ int onepose_match_cached_stages(const void* packed_weights, const void* desc2d, 
              "match_cached: precision %d", precision);
   OP_REQUIRE((object_flags & ~ONEPOSE_OBJ_GAT_TABLES) == 0, "match_cached: flags %d",
              object_flags);
-  int rc = check_match_args(packed_weights, desc2d, object_cache, leaves_prepared, batch, n1, n3,
-                            num_leaf, scale_factor, matches0, matches1, mscores0, mscores1,
-                            workspace);
-  if (rc != ONEPOSE_OK) return rc;
-  CacheHdr hdr;
-  {
-    std::lock_guard<std::mutex> lk(g_cache_mu);
-    const auto it = g_caches.find(object_cache);
-    OP_REQUIRE(it != g_caches.end(),
-               "match_cached: object_cache was not built by onepose_object_prepare (or was "
-               "released)");
-    const CacheRecord& c = it->second;
-    OP_REQUIRE(c.n3 == n3 && c.num_leaf == num_leaf && c.precision == precision &&
-                   c.flags == object_flags,
-               "match_cached: cache prepared for n3=%d num_leaf=%d precision=%d flags=%d, "
-               "called with n3=%d num_leaf=%d precision=%d flags=%d",
-               c.n3, c.num_leaf, c.precision, c.flags, n3, num_leaf, precision, object_flags);
-    hdr = cache_hdr(c.n3, c.num_leaf, c.precision, c.flags, c.gen);
-  }
-  const bool planes = precision != ONEPOSE_PREC_FP32;
-  const Plan need = make_plan(nullptr, batch, n1, n3, num_leaf, conf != nullptr, planes);
-  if (workspace_bytes < need.bytes) {
-    set_error("match_cached: workspace %zu < %zu bytes", workspace_bytes, need.bytes);
-    return ONEPOSE_ERR_WORKSPACE;
-  }
-  const Plan p = make_plan(workspace, batch, n1, n3, num_leaf, conf != nullptr, planes);
-  return match_impl(packed_weights, desc2d, desc2d_bstride, object_cache, 0, leaves_prepared,
-                    prepared_bstride, batch, n1, n3, num_leaf, scale_factor, match_threshold,
-                    matches0, matches1, mscores0, mscores1, conf, p,
-                    static_cast<hipStream_t>(stream_), precision, nullptr, object_cache,
-                    object_flags, desc_dtype, &hdr, first_stage, last_stage);
+  MatchCall c;
+  c.weights = packed_weights; c.stream = static_cast<hipStream_t>(stream_);
+  c.desc2d = desc2d; c.desc2d_bs = desc2d_bstride; c.desc_dt = desc_dtype;
+  c.desc3d = object_cache; c.desc3d_bs = 0;
+  c.obj_cache = object_cache; c.obj_flags = object_flags;
+  c.leaves_pm = leaves_prepared; c.leaves_pm_bs = prepared_bstride;
+  c.batch = batch; c.n1 = n1; c.n3 = n3; c.num_leaf = num_leaf;
+  c.scale_factor = scale_factor; c.match_threshold = match_threshold; c.precision = precision;
+  c.matches0 = matches0; c.matches1 = matches1; c.mscores0 = mscores0; c.mscores1 = mscores1;
+  c.conf = conf;
+  c.first_stage = first_stage; c.last_stage = last_stage;
+  Plan p;
+  const int rc = checked_plan("match_cached", &c, leaves_prepared, workspace, workspace_bytes, &p);
+  return rc != ONEPOSE_OK ? rc : match_impl(c, p);
 }
 
 int onepose_match_workspace_region(int batch, int n1, int n3, int num_leaf, int with_conf,
@@ -3000,7 +2675,8 @@ size_t onepose_match_sharded_workspace_bytes(int batch, int n1, int n3_total, in
   int s0, n3s;
   shard_range(n3_total, world, rank, &s0, &n3s);
   if (n3s <= 0) return 0;
-  return make_plan(nullptr, batch, n1, n3s, num_leaf, with_conf != 0).bytes +
+  // planes = true: this size has always included the activation planes, in every precision
+  return make_plan(nullptr, batch, n1, n3s, num_leaf, with_conf != 0, true).bytes +
          align_up((size_t)batch * n3_total * 8, 256);
 }
 
@@ -3021,22 +2697,6 @@ int onepose_match_sharded(const void* packed_weights, const float* desc2d, int64
   int off, n3s;
   shard_range(n3_total, world, rank, &off, &n3s);
   OP_REQUIRE(n3s >= 1, "match_sharded: empty shard (n3_total %d, world %d)", n3_total, world);
-  int rc = check_match_args(packed_weights, desc2d, desc3d_shard, leaves_shard_prepared, batch, n1,
-                            n3s, num_leaf, scale_factor, matches0, matches1, mscores0, mscores1,
-                            workspace);
-  if (rc != ONEPOSE_OK) return rc;
-  const size_t need_x = shard_xchg_bytes(batch, n1, n3_total, world);
-  if (xchg_bytes < need_x) {
-    set_error("match_sharded: exchange buffers %zu < %zu bytes per rank", xchg_bytes, need_x);
-    return ONEPOSE_ERR_WORKSPACE;
-  }
-  const size_t need = onepose_match_sharded_workspace_bytes(batch, n1, n3_total, world, rank,
-                                                            num_leaf, conf_shard != nullptr);
-  if (workspace_bytes < need) {
-    set_error("match_sharded: workspace %zu < %zu bytes", workspace_bytes, need);
-    return ONEPOSE_ERR_WORKSPACE;
-  }
-  const Plan p = make_plan(workspace, batch, n1, n3s, num_leaf, conf_shard != nullptr);
   ShardCtx sh;
   sh.world = world;
   sh.rank = rank;
@@ -3048,12 +2708,24 @@ int onepose_match_sharded(const void* packed_weights, const float* desc2d, int64
   sh.cap = xchg_bytes;
   sh.fn = allgather;
   sh.user = user;
+  sh.colbest_full = nullptr;   // behind the plan, below
+  MatchCall c;
+  c.weights = packed_weights; c.stream = static_cast<hipStream_t>(stream_);
+  c.desc2d = desc2d; c.desc2d_bs = desc2d_bstride;
+  c.desc3d = desc3d_shard; c.desc3d_bs = desc3d_bstride;
+  c.leaves_pm = leaves_shard_prepared; c.leaves_pm_bs = prepared_bstride;
+  c.batch = batch; c.n1 = n1; c.n3 = n3s; c.num_leaf = num_leaf;
+  c.scale_factor = scale_factor; c.match_threshold = match_threshold; c.precision = precision;
+  c.matches0 = matches0; c.matches1 = matches1; c.mscores0 = mscores0; c.mscores1 = mscores1;
+  c.conf = conf_shard;
+  c.shard = &sh;
+  Plan p;
+  const int rc = checked_plan("match_sharded", &c, leaves_shard_prepared, workspace,
+                              workspace_bytes, &p);
+  if (rc != ONEPOSE_OK) return rc;
   sh.colbest_full = reinterpret_cast<unsigned long long*>(static_cast<char*>(workspace) +
                                                           align_up(p.bytes, 256));
-  return match_impl(packed_weights, desc2d, desc2d_bstride, desc3d_shard, desc3d_bstride,
-                    leaves_shard_prepared, prepared_bstride, batch, n1, n3s, num_leaf, scale_factor,
-                    match_threshold, matches0, matches1, mscores0, mscores1, conf_shard, p,
-                    static_cast<hipStream_t>(stream_), precision, &sh);
+  return match_impl(c, p);
 }
 
 }  // extern "C"

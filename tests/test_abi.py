@@ -281,6 +281,166 @@ def test_match_cached_stages_rejects_bad_ranges():
         assert b"stages" in lib.onepose_last_error()
 
 
+def test_matcher_entry_points_refuse_in_order():
+    """Every refusal a matcher entry point makes before it touches the device: its status code, a
+    distinguishing part of onepose_last_error(), and which refusal wins when two apply.  The
+    pointers are dummies that no refused call dereferences (no device needed).  One refusal is
+    out of reach here: onepose_match_cached_stages checks the cache registry before the
+    workspace size, and only onepose_object_prepare (a device call) registers a cache."""
+    from onepose_amd import _lib
+    lib = _lib.load()
+    P = 0x1000   # never dereferenced
+    INVALID, WORKSPACE = 1, 4
+    gather = _lib.ALLGATHER_FN(lambda nbytes, stream, user: 0)
+    B, n1, n3, L = 2, 70, 130, 5
+    ws = lib.onepose_match_workspace_bytes_ex(B, n1, n3, L, 1, 0)
+    ws_split = lib.onepose_match_workspace_bytes_ex(B, n1, n3, L, 0, 2)
+    ws_obj = lib.onepose_object_prepare_workspace_bytes(n3, L)
+    ws_sh = lib.onepose_match_sharded_workspace_bytes(B, n1, n3, 2, 1, L, 1)
+    xb = lib.onepose_match_sharded_xchg_bytes(B, n1, n3, 2)
+    assert min(ws, ws_split, ws_obj, ws_sh, xb) > 0
+
+    def run(fn, good, rows):
+        names = list(good)
+        for change, code, text in rows:
+            assert set(change) <= set(names), change
+            args = [{**good, **change}[k] for k in names]
+            rc = getattr(lib, fn)(*args)
+            err = lib.onepose_last_error().decode()
+            assert rc == code and text in err, (fn, change, rc, err)
+
+    out = dict(m0=P, m1=P, s0=P, s1=P, conf=P)
+    shape = dict(batch=B, n1=n1, n3=n3, L=L, scale=1.0, thr=0.2)
+    common = [  # check_match_args, shared by the four match entry points
+        (dict(w=None), INVALID, "match: null input"),
+        (dict(d2=None), INVALID, "match: null input"),
+        (dict(leaves=None), INVALID, "match: null input"),
+        (dict(m0=None), INVALID, "match: null output"),
+        (dict(s1=None), INVALID, "match: null output"),
+        (dict(batch=0), INVALID, "match: batch=0 n1=70"),
+        (dict(n1=0), INVALID, "match: batch=2 n1=0"),
+        (dict(L=17), INVALID, "match: num_leaf=17 not in [1,16]"),
+        (dict(L=0), INVALID, "match: num_leaf=0 not in [1,16]"),
+        (dict(scale=0.0), INVALID, "match: scale_factor 0"),
+        (dict(ws=None), INVALID, "match: null workspace"),
+        (dict(w=None, m0=None), INVALID, "match: null input"),
+        (dict(m1=None, batch=0), INVALID, "match: null output"),
+        (dict(batch=0, L=17), INVALID, "match: batch=0"),
+        (dict(L=17, scale=0.0), INVALID, "match: num_leaf=17"),
+        (dict(scale=0.0, ws=None), INVALID, "match: scale_factor 0"),
+        (dict(ws=None, wsb=0), INVALID, "match: null workspace"),
+    ]
+
+    good = dict(w=P, d2=P, d2bs=256 * n1, d3=P, d3bs=256 * n3, leaves=P, lbs=0, dtype=0, **shape,
+                prec=0, **out, ws=P, wsb=ws, stream=None)
+    run("onepose_match_dt", good, common + [
+        (dict(prec=7), INVALID, "match: precision 7"),
+        (dict(prec=-1), INVALID, "match: precision -1"),
+        (dict(dtype=5), INVALID, "match: dtype 5"),
+        (dict(d3=None), INVALID, "match: null input"),
+        (dict(n3=0), INVALID, "match: batch=2 n1=70 n3=0"),
+        (dict(wsb=ws - 1), WORKSPACE, f"match: workspace {ws - 1} < {ws} bytes"),
+        (dict(wsb=0), WORKSPACE, f"match: workspace 0 < {ws} bytes"),
+        (dict(prec=2, conf=None, wsb=ws_split - 1), WORKSPACE,
+         f"match: workspace {ws_split - 1} < {ws_split} bytes"),
+        (dict(prec=7, dtype=5), INVALID, "match: precision 7"),
+        (dict(dtype=5, w=None), INVALID, "match: dtype 5"),
+        (dict(prec=3, ws=None), INVALID, "match: precision 3"),
+        (dict(batch=0, wsb=0), INVALID, "match: batch=0"),
+    ])
+
+    good = dict(w=P, d2=P, d2bs=256 * n1, d3=P, d3bs=256 * n3, leaves=P, lbs=0, **shape, prec=0,
+                **out, ws=P, wsb=ws, stream=None)
+    run("onepose_match_prepared_ex", good, common + [
+        (dict(prec=7), INVALID, "match: precision 7"),
+        (dict(d3=None), INVALID, "match: null input"),
+        (dict(wsb=ws - 1), WORKSPACE, f"match: workspace {ws - 1} < {ws} bytes"),
+        (dict(prec=2, conf=None, wsb=ws_split - 1), WORKSPACE,
+         f"match: workspace {ws_split - 1} < {ws_split} bytes"),
+        (dict(prec=7, w=None), INVALID, "match: precision 7"),
+        (dict(scale=0.0, wsb=0), INVALID, "match: scale_factor 0"),
+    ])
+
+    good = dict(w=P, d2=P, dtype=0, d2bs=256 * n1, cache=P, leaves=P, lbs=0, **shape, prec=0,
+                flags=0, **out, ws=P, wsb=ws, first=0, last=15, stream=None)
+    unregistered = "match_cached: object_cache was not built by onepose_object_prepare"
+    run("onepose_match_cached_stages", good, common + [
+        (dict(first=5, last=4), INVALID, "match_cached: stages [5, 4]"),
+        (dict(dtype=5), INVALID, "match_cached: dtype 5"),
+        (dict(prec=7), INVALID, "match_cached: precision 7"),
+        (dict(flags=2), INVALID, "match_cached: flags 2"),
+        (dict(flags=-1), INVALID, "match_cached: flags -1"),
+        (dict(cache=None), INVALID, "match: null input"),
+        (dict(), INVALID, unregistered),
+        (dict(flags=1), INVALID, unregistered),
+        (dict(last=16, dtype=5), INVALID, "match_cached: stages [0, 16]"),
+        (dict(dtype=5, prec=7), INVALID, "match_cached: dtype 5"),
+        (dict(prec=7, flags=2), INVALID, "match_cached: precision 7"),
+        (dict(flags=2, w=None), INVALID, "match_cached: flags 2"),
+        (dict(ws=None, cache=0x2000), INVALID, "match: null workspace"),
+        (dict(wsb=0), INVALID, unregistered),
+    ])
+
+    good = dict(w=P, d2=P, d2bs=256 * n1, d3=P, d3bs=256 * n3, leaves=P, lbs=0, batch=B, n1=n1,
+                n3=n3, L=L, world=2, rank=1, scale=1.0, thr=0.2, prec=0, send=P, recv=P, xb=xb,
+                fn=gather, user=None, **out, ws=P, wsb=ws_sh, stream=None)
+    short_x = f"match_sharded: exchange buffers {xb - 1} < {xb} bytes per rank"
+    run("onepose_match_sharded", good, common + [
+        (dict(prec=7), INVALID, "match_sharded: precision 7"),
+        (dict(rank=2), INVALID, "match_sharded: rank 2 of 2"),
+        (dict(world=0, rank=0), INVALID, "match_sharded: rank 0 of 0"),
+        (dict(send=None), INVALID, "match_sharded: null exchange buffer/callback"),
+        (dict(recv=None), INVALID, "match_sharded: null exchange buffer/callback"),
+        (dict(fn=_lib.ALLGATHER_FN()), INVALID, "match_sharded: null exchange buffer/callback"),
+        (dict(n3=1, rank=0), INVALID, "match_sharded: empty shard (n3_total 1, world 2)"),
+        (dict(d3=None), INVALID, "match: null input"),
+        (dict(xb=xb - 1), WORKSPACE, short_x),
+        (dict(wsb=ws_sh - 1), WORKSPACE, f"match_sharded: workspace {ws_sh - 1} < {ws_sh} bytes"),
+        (dict(prec=7, rank=2), INVALID, "match_sharded: precision 7"),
+        (dict(rank=-1, send=None), INVALID, "match_sharded: rank -1 of 2"),
+        (dict(send=None, n3=1, rank=0), INVALID, "match_sharded: null exchange"),
+        (dict(n3=1, rank=0, w=None), INVALID, "match_sharded: empty shard"),
+        (dict(ws=None, xb=0), INVALID, "match: null workspace"),
+        (dict(xb=xb - 1, wsb=0), WORKSPACE, short_x),
+    ])
+
+    good = dict(w=P, d3=P, dtype=0, leaves=P, n3=n3, L=L, prec=0, flags=0, cache=P, ws=P,
+                wsb=ws_obj, stream=None)
+    run("onepose_object_prepare_dt", good, [
+        (dict(dtype=5), INVALID, "object_prepare: dtype 5"),
+        (dict(w=None), INVALID, "object_prepare: null pointer"),
+        (dict(d3=None), INVALID, "object_prepare: null pointer"),
+        (dict(leaves=None), INVALID, "object_prepare: null pointer"),
+        (dict(cache=None), INVALID, "object_prepare: null pointer"),
+        (dict(prec=7), INVALID, "object_prepare: precision 7"),
+        (dict(n3=0), INVALID, "object_prepare: n3=0 num_leaf=5"),
+        (dict(L=17), INVALID, "object_prepare: n3=130 num_leaf=17"),
+        (dict(flags=2), INVALID, "object_prepare: flags 2"),
+        (dict(ws=None), INVALID, "object_prepare: null workspace"),
+        (dict(wsb=ws_obj - 1), WORKSPACE,
+         f"object_prepare: workspace {ws_obj - 1} < {ws_obj} bytes"),
+        (dict(dtype=5, w=None), INVALID, "object_prepare: dtype 5"),
+        (dict(cache=None, prec=7), INVALID, "object_prepare: null pointer"),
+        (dict(prec=7, L=17), INVALID, "object_prepare: precision 7"),
+        (dict(L=17, flags=2), INVALID, "object_prepare: n3=130 num_leaf=17"),
+        (dict(flags=2, ws=None), INVALID, "object_prepare: flags 2"),
+        (dict(ws=None, wsb=0), INVALID, "object_prepare: null workspace"),
+    ])
+
+    good = dict(leaves=P, dtype=0, lbs=0, batch=B, n3=n3, L=L, out=P, stream=None)
+    run("onepose_prepare_leaves_dt", good, [
+        (dict(leaves=None), INVALID, "prepare_leaves: null pointer"),
+        (dict(out=None), INVALID, "prepare_leaves: null pointer"),
+        (dict(dtype=5), INVALID, "prepare_leaves: dtype 5"),
+        (dict(batch=0), INVALID, "prepare_leaves: batch=0 n3=130 num_leaf=5"),
+        (dict(n3=0), INVALID, "prepare_leaves: batch=2 n3=0"),
+        (dict(L=17), INVALID, "prepare_leaves: batch=2 n3=130 num_leaf=17"),
+        (dict(L=0), INVALID, "prepare_leaves: batch=2 n3=130 num_leaf=0"),
+        (dict(out=None, dtype=5), INVALID, "prepare_leaves: null pointer"),
+        (dict(dtype=5, batch=0), INVALID, "prepare_leaves: dtype 5"),
+    ])
+
+
 @pytest.mark.parametrize("prec", [0, 2])
 @pytest.mark.parametrize("B,n1,n3,L", [(1, 65, 97, 8), (6, 200, 330, 6)])
 def test_match_workspace_region(B, n1, n3, L, prec):

@@ -10,7 +10,8 @@ import pytest
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 REPO = os.path.dirname(HERE)
-SRCS = ("matcher", "gemm", "pnp", "frame_ops", "superpoint", "superglue")
+SRCS = ("matcher", "matcher_pack", "runtime", "gemm", "pnp", "frame_ops", "superpoint",
+        "superglue")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 
 

@@ -5,9 +5,13 @@ compared bit for bit.  Each build runs in its own process (ONEPOSE_LIB selects t
     python tools/bitcmp.py cmp /tmp/a.npz /tmp/b.npz
 Cases: the uncached forward (onepose_match_ex, conf) and the cached bench path
 (onepose_object_prepare + onepose_match_cached, with and without GAT tables) in fp32, bf16 and
-fp32_split, on ragged and batched shapes.  BITCMP_BIG=1 adds configs 5 and 3's shapes (2048 x
-8192, 1024 x 16384: more than 64 score tiles per row); their conf matrices are compared by
-SHA-256 digest."""
+fp32_split, on ragged and batched shapes (one with a batch above the fused KV fold's limit and
+n3 % 4 != 0), and a world-size-1 sharded frame (onepose_amd.sharded.ShardedMatcher, fp32 and
+fp32_split).  The launch-kind sequence of each case's first uncached, cached and sharded call
+(onepose_profile_begin / _end) is dumped too: equal sequences show the launch order did not
+move.  BITCMP_BIG=1 adds configs 5 and 3's shapes (2048 x 8192, 1024 x 16384: more than 64 score
+tiles per row); their conf matrices are compared by SHA-256 digest."""
+import ctypes
 import hashlib
 import os
 import sys
@@ -16,7 +20,9 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
 import torch
 
-CASES = [(1024, 4096, 8, 1), (200, 777, 8, 2), (96, 300, 3, 1), (256, 1024, 12, 3)]
+CASES = [(1024, 4096, 8, 1), (200, 777, 8, 2), (96, 300, 3, 1), (256, 1024, 12, 3),
+         (64, 130, 3, 5)]   # (n1, n3, num_leaf, batch)
+SHARDED = [(96, 300, 3, 1)]   # world size 1, no process group
 PRECS = ["fp32", "bf16", "fp32_split"]
 if os.environ.get("BITCMP_BIG") == "1":
     CASES += [(2048, 8192, 8, 1), (1024, 16384, 8, 1)]
@@ -29,11 +35,39 @@ def _conf(c):
     return x
 
 
+def _kinds(lib, call, cap=1024):
+    """call()'s result and the kinds of the launches it made, in order."""
+    from onepose_amd import _lib
+    _lib.check(lib.onepose_profile_begin(2 ** 64 - 1, cap), "profile_begin")
+    try:
+        res = call()
+    finally:
+        kinds, n = np.full(cap, -1, np.int32), ctypes.c_int(0)
+        rc = lib.onepose_profile_end(kinds.ctypes.data, None, cap, ctypes.byref(n))
+    _lib.check(rc, "profile_end")
+    assert 0 < n.value <= cap, n.value
+    return res, kinds[:n.value].copy()
+
+
 def dump(path):
-    from onepose_amd import _lib, matcher, synthetic as S
+    from onepose_amd import _lib, matcher, sharded, synthetic as S
     dev = torch.device("cuda", 0)
     lib = _lib.load()
     out = {}
+    for (n1, n3, L, B) in SHARDED:
+        sd = S.make_state_dict(1)
+        data, _, _ = S.make_matcher_inputs(n1, n3, L, seed=3, batch=B)
+        for prec in ("fp32", "fp32_split"):
+            m = matcher.from_state_dict(sd, {**S.DEFAULT_HPARAMS, "attention_precision": prec}).to(dev)
+            sm = sharded.ShardedMatcher(m, None, data["descriptors3d_db"][0],
+                                        data["descriptors2d_db"][0], n1, dev, batch=B)
+            d2 = torch.from_numpy(data["descriptors2d_query"]).to(dev)
+            res, kinds = _kinds(lib, lambda: sm.match(d2))
+            torch.cuda.synchronize()
+            key = f"s_{n1}_{n3}_{L}_{B}_{prec}"
+            for nm, x in zip(("m0", "m1", "s0", "s1"), res):
+                out[f"{key}_{nm}"] = x.cpu().numpy()
+            out[f"{key}_kinds"] = kinds
     for (n1, n3, L, B) in CASES:
         sd = S.make_state_dict(1)
         data, _, _ = S.make_matcher_inputs(n1, n3, L, seed=3, batch=B)
@@ -41,8 +75,9 @@ def dump(path):
         for pi, prec in enumerate(PRECS):
             m = matcher.from_state_dict(sd, {**S.DEFAULT_HPARAMS, "attention_precision": prec}).to(dev)
             with torch.no_grad():
-                pred, conf = m(t)
+                (pred, conf), kinds = _kinds(lib, lambda: m(t))
             key = f"u_{n1}_{n3}_{L}_{B}_{prec}"
+            out[f"{key}_kinds"] = kinds
             for k, v in pred.items():
                 out[f"{key}_{k}"] = v.cpu().numpy()
             out[f"{key}_conf"] = _conf(conf)
@@ -68,14 +103,15 @@ def dump(path):
                 cf = torch.empty(B, n1, n3, **f32)
                 wmb = lib.onepose_match_workspace_bytes(B, n1, n3, L, 1)
                 wm = torch.empty(wmb, dtype=torch.uint8, device=dev)
-                _lib.check(lib.onepose_match_cached(
+                rc, kinds = _kinds(lib, lambda: lib.onepose_match_cached(
                     w.data_ptr(), d2.data_ptr(), 256 * n1, cache.data_ptr(), pmv.data_ptr(), 0, B,
                     n1, n3, L, float(m.hparams["scale_factor"]), float(m.hparams["match_threshold"]),
-                    pi, flags, *[x.data_ptr() for x in o], cf.data_ptr(), wm.data_ptr(), wmb, s),
-                    "match_cached")
+                    pi, flags, *[x.data_ptr() for x in o], cf.data_ptr(), wm.data_ptr(), wmb, s))
+                _lib.check(rc, "match_cached")
                 torch.cuda.synchronize()
                 lib.onepose_object_release(cache.data_ptr())
                 ck = f"c{flags}_{n1}_{n3}_{L}_{B}_{prec}"
+                out[f"{ck}_kinds"] = kinds
                 for nm, x in zip(("m0", "m1", "s0", "s1"), o):
                     out[f"{ck}_{nm}"] = x.cpu().numpy()
                 out[f"{ck}_conf"] = _conf(cf)
