@@ -60,7 +60,7 @@ const char* onepose_last_error(void);
 /* ABI version, bumped on any signature change or new entry point (4: the per-precision
  * workspace and object-cache size queries; 5: the object cache's device-side header and
  * onepose_device_errors; 6: onepose_match_cached_stages; 7:
- * onepose_match_workspace_region; 8: onepose_pnp_max_points). */
+ * onepose_match_workspace_region; 8: onepose_pnp_max_points; 9: onepose_superpoint_layer). */
 int onepose_abi_version(void);
 /* (ABI 5) The library's sticky device-side error bits (ONEPOSE_DEVERR_*), set by kernels that
  * cannot return a status: *bits receives them, and `clear` != 0 resets them.  Synchronises with
@@ -481,6 +481,19 @@ int onepose_superpoint_detect(const float* score_map, const float* dense_desc, i
                               int max_keypoints, int align_corners, float* keypoints,
                               float* scores, float* descriptors, int* counts, void* workspace,
                               size_t workspace_bytes, void* stream);
+/* (ABI 9) One convolution layer of the network alone, for stage-by-stage checks: layer 0 =
+ * conv1a .. 11 = convDb (onepose_superpoint_tensor_name order), launched exactly as
+ * onepose_superpoint launches it -- the same kernel, tile, fused 2x2 max-pool (layers 1, 3, 5)
+ * and epilogue (ReLU; softmax over 65 + pixel shuffle for convPb; bias only for convDb).
+ * h, w are the layer's input map size (any >= 1 with h * w * 256 < 2^31; even for the pooled
+ * layers).  x is NHWC
+ * [batch][h][w][cin] ([batch][h][w] for layer 0); y receives NHWC [batch][h][w][cout],
+ * [batch][h/2][w/2][cout] for a pooled layer, or the score map [batch][8h][8w] for layer 9:
+ * onepose_superpoint_layer_out_floats(layer, h, w) floats per sample (0 for a refused
+ * layer or size).  All device pointers. */
+size_t onepose_superpoint_layer_out_floats(int layer, int h, int w);
+int onepose_superpoint_layer(const void* packed, int layer, const float* x, int batch, int h,
+                             int w, float* y, void* stream);
 
 /* ------------------------------------------------------------------------------------ *
  * SuperGlue 2D-2D matcher  --  replaces SuperGlue.forward
@@ -488,8 +501,8 @@ int onepose_superpoint_detect(const float* score_map, const float* dense_desc, i
  *    attention layers, the final projection, log_optimal_transport and the mutual check;
  *    reached from inference_demo.py's LocalFeatureObjectDetector and src/sfm/match_features.py)
  * fp32 only.  This family is versioned on its own: onepose_superglue_version() returns 1 and
- * is bumped when one of the entry points below changes, while onepose_abi_version() stays 8 --
- * nothing that existed at ABI 8 changed, and a caller of the GATsSPG / pose entry points need
+ * is bumped when one of the entry points below changes; onepose_abi_version() was not bumped
+ * for it -- nothing that existed at ABI 8 changed, and a caller of the GATsSPG / pose entry points need
  * not rebuild for a matcher it does not use.
  * ------------------------------------------------------------------------------------ */
 int onepose_superglue_version(void);

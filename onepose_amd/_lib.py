@@ -20,7 +20,7 @@ c_void_p, c_char_p = ctypes.c_void_p, ctypes.c_char_p
 
 # onepose_allgather_fn: int (*)(size_t bytes_per_rank, void* stream, void* user)
 ALLGATHER_FN = ctypes.CFUNCTYPE(c_int, c_size_t, c_void_p, c_void_p)
-ABI_VERSION = 8
+ABI_VERSION = 9
 DEVERR_STALE_CACHE = 1   # ONEPOSE_DEVERR_STALE_CACHE
 STAGE_INPUTS, STAGE_LAYER0, STAGE_FINAL, STAGE_SCORE, STAGE_WINNERS = 0, 1, 13, 14, 15  # ABI 6
 REGION_STATE2D, REGION_STATE3D, REGION_DESC2D, REGION_DESC3D = 0, 1, 2, 3   # ABI 7
@@ -129,6 +129,9 @@ PROTOTYPES = {
     "onepose_superpoint_detect": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_float,
                                           c_int, c_int, c_int, c_void_p, c_void_p, c_void_p,
                                           c_void_p, c_void_p, c_size_t, c_void_p]),
+    "onepose_superpoint_layer_out_floats": (c_size_t, [c_int, c_int, c_int]),   # ABI 9
+    "onepose_superpoint_layer": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_void_p,
+                                         c_void_p]),
     "onepose_superglue_version": (c_int, []),
     "onepose_superglue_num_tensors": (c_int, []),
     "onepose_superglue_tensor_name": (c_char_p, [c_int]),

@@ -81,7 +81,7 @@ using namespace onepose;
 extern "C" {
 
 const char* onepose_last_error(void) { return g_last_error.c_str(); }
-int onepose_abi_version(void) { return 8; }
+int onepose_abi_version(void) { return 9; }
 
 int onepose_profile_begin(uint64_t kind_mask, int capacity) {
   clear_error();

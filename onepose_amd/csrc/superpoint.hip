@@ -1016,6 +1016,35 @@ int big_conv(const float* x, int B, int H, int W, const float* packed, int layer
   return conv_launch<CIN, 3, TileBig, POOL, CE_RELU>(x, B, H, W, packed, layer, y, st);
 }
 
+// Layer `layer` (0 = conv1a .. 11 = convDb) on its input map x [B][H][W][cin] (conv1a: the
+// image [B][H][W]): the one place that picks each layer's kernel, tile, fused pool and
+// epilogue, shared by the forward and onepose_superpoint_layer.
+int run_layer(int layer, const float* x, int B, int H, int W, const float* P, float* y,
+              hipStream_t st) {
+  switch (layer) {
+    case 0:
+      OP_LAUNCH(K_SP_CONV, st, conv1a_kernel, dim3(ceil_div(H * W, 64), B), dim3(256), 0, st, x,
+                (int64_t)H * W, P + layer_offset(0), P + layer_offset(0) + 64 * 9, H, W, y,
+                (int64_t)H * W * 64);
+      return ONEPOSE_OK;
+    case 1: return big_conv<64, true>(x, B, H, W, P, 1, y, st);
+    case 2: return big_conv<64, false>(x, B, H, W, P, 2, y, st);
+    case 3: return big_conv<64, true>(x, B, H, W, P, 3, y, st);
+    case 4: return big_conv<64, false>(x, B, H, W, P, 4, y, st);
+    case 5: return big_conv<128, true>(x, B, H, W, P, 5, y, st);
+    case 6:
+    case 7:
+    case 8:
+    case 10: return conv_launch<128, 3, TileSmall, false, CE_RELU>(x, B, H, W, P, layer, y, st);
+    case 9: return conv_launch<256, 1, TileHead, false, CE_SOFTMAX>(x, B, H, W, P, 9, y, st);
+    case 11: return conv_launch<256, 1, TileSmall, false, CE_BIAS>(x, B, H, W, P, 11, y, st);
+  }
+  set_error("superpoint: layer %d not in [0, %d)", layer, kSpLayers);
+  return ONEPOSE_ERR_INVALID;
+}
+
+bool layer_pools(int layer) { return layer == 1 || layer == 3 || layer == 5; }
+
 constexpr int kMaxSortKeypoints = 16384;
 
 int check_detect_args(int batch, int h, int w, int nms_radius, int remove_borders,
@@ -1171,36 +1200,20 @@ int onepose_superpoint(const void* packed, const float* image, int batch, int h,
   const float* P = static_cast<const float*>(packed);
   const int B = batch;
   // shared encoder: conv1a, [1b+pool], 2a, [2b+pool], 3a, [3b+pool], 4a, 4b
-  OP_LAUNCH(K_SP_CONV, st, conv1a_kernel, dim3(ceil_div(h * w, 64), B), dim3(256), 0, st, image,
-            (int64_t)h * w, P + layer_offset(0), P + layer_offset(0) + 64 * 9, h, w, p.f0,
-            (int64_t)h * w * 64);
-  if ((rc = big_conv<64, true>(p.f0, B, h, w, P, 1, p.f1, st))) return rc;
-  if ((rc = big_conv<64, false>(p.f1, B, h / 2, w / 2, P, 2, p.f0, st)))
-    return rc;
-  if ((rc = big_conv<64, true>(p.f0, B, h / 2, w / 2, P, 3, p.f1, st)))
-    return rc;
-  if ((rc = big_conv<64, false>(p.f1, B, h / 4, w / 4, P, 4, p.f0, st)))
-    return rc;
-  if ((rc = big_conv<128, true>(p.f0, B, h / 4, w / 4, P, 5, p.f1, st)))
-    return rc;
-  if ((rc = conv_launch<128, 3, TileSmall, false, CE_RELU>(p.f1, B, h / 8, w / 8, P, 6, p.f0, st)))
-    return rc;
-  if ((rc = conv_launch<128, 3, TileSmall, false, CE_RELU>(p.f0, B, h / 8, w / 8, P, 7, p.x4, st)))
-    return rc;
+  if ((rc = run_layer(0, image, B, h, w, P, p.f0, st))) return rc;
+  if ((rc = run_layer(1, p.f0, B, h, w, P, p.f1, st))) return rc;
+  if ((rc = run_layer(2, p.f1, B, h / 2, w / 2, P, p.f0, st))) return rc;
+  if ((rc = run_layer(3, p.f0, B, h / 2, w / 2, P, p.f1, st))) return rc;
+  if ((rc = run_layer(4, p.f1, B, h / 4, w / 4, P, p.f0, st))) return rc;
+  if ((rc = run_layer(5, p.f0, B, h / 4, w / 4, P, p.f1, st))) return rc;
+  if ((rc = run_layer(6, p.f1, B, h / 8, w / 8, P, p.f0, st))) return rc;
+  if ((rc = run_layer(7, p.f0, B, h / 8, w / 8, P, p.x4, st))) return rc;
   // score head: convPa + ReLU, convPb -> softmax(65)[:64] -> pixel shuffle -> [H][W]
-  if ((rc = conv_launch<128, 3, TileSmall, false, CE_RELU>(p.x4, B, h / 8, w / 8, P, 8, p.head,
-                                                           st)))
-    return rc;
-  if ((rc = conv_launch<256, 1, TileHead, false, CE_SOFTMAX>(p.head, B, h / 8, w / 8, P, 9,
-                                                             p.score, st)))
-    return rc;
+  if ((rc = run_layer(8, p.x4, B, h / 8, w / 8, P, p.head, st))) return rc;
+  if ((rc = run_layer(9, p.head, B, h / 8, w / 8, P, p.score, st))) return rc;
   // descriptor head: convDa + ReLU, convDb, normalise (the score head's hidden map is dead)
-  if ((rc = conv_launch<128, 3, TileSmall, false, CE_RELU>(p.x4, B, h / 8, w / 8, P, 10, p.head,
-                                                           st)))
-    return rc;
-  if ((rc = conv_launch<256, 1, TileSmall, false, CE_BIAS>(p.head, B, h / 8, w / 8, P, 11,
-                                                           p.dense, st)))
-    return rc;
+  if ((rc = run_layer(10, p.x4, B, h / 8, w / 8, P, p.head, st))) return rc;
+  if ((rc = run_layer(11, p.head, B, h / 8, w / 8, P, p.dense, st))) return rc;
   const int cells = B * (h / 8) * (w / 8);
   OP_LAUNCH(K_SP_DESC, st, desc_norm_kernel, dim3(ceil_div(cells, 4)), dim3(256), 0, st, p.dense,
             cells);
@@ -1215,6 +1228,32 @@ int onepose_superpoint(const void* packed, const float* image, int batch, int h,
     OP_HIP(hipMemcpyAsync(dense_desc, p.dense, sizeof(float) * cells * 256,
                           hipMemcpyDeviceToDevice, st));
   return ONEPOSE_OK;
+}
+
+size_t onepose_superpoint_layer_out_floats(int layer, int h, int w) {
+  if (layer < 0 || layer >= kSpLayers || h < 1 || w < 1) return 0;
+  if ((int64_t)h * w * 256 > INT32_MAX) return 0;
+  if (layer == 9) return (size_t)64 * h * w;
+  if (layer_pools(layer)) return (size_t)(h / 2) * (w / 2) * kSp[layer].cout;
+  return (size_t)h * w * kSp[layer].cout;
+}
+
+int onepose_superpoint_layer(const void* packed, int layer, const float* x, int batch, int h,
+                             int w, float* y, void* stream) {
+  clear_error();
+  OP_REQUIRE(packed && x && y, "superpoint_layer: null pointer");
+  OP_REQUIRE(layer >= 0 && layer < kSpLayers, "superpoint_layer: layer %d not in [0, %d)", layer,
+             kSpLayers);
+  OP_REQUIRE(batch >= 1 && h >= 1 && w >= 1, "superpoint_layer: map %dx%d (batch %d)", h, w,
+             batch);
+  // the kernels index a sample's pixels x channels with 32-bit ints
+  OP_REQUIRE((int64_t)h * w * 256 <= INT32_MAX, "superpoint_layer: map %dx%d is too large", h,
+             w);
+  OP_REQUIRE(!layer_pools(layer) || (h % 2 == 0 && w % 2 == 0),
+             "superpoint_layer: %s pools 2x2, map %dx%d must have even sides", kSpNames[layer], h,
+             w);
+  return run_layer(layer, x, batch, h, w, static_cast<const float*>(packed), y,
+                   static_cast<hipStream_t>(stream));
 }
 
 size_t onepose_superpoint_detect_workspace_bytes(int batch, int h, int w) {

@@ -206,6 +206,49 @@ class SuperPoint:
     __call__ = forward
 
 
+POOLED_LAYERS = (1, 3, 5)   # conv1b, conv2b, conv3b end in the fused 2x2 max-pool
+
+
+def pack_state_dict(sd, device):
+    """The 24 tensors of a SuperPoint state dict, packed for the kernels, on ``device``."""
+    m = SuperPoint()
+    m.load_state_dict(sd)
+    return m.to(device).packed_weights()
+
+
+def run_layer(packed, layer: int, x):
+    """One convolution layer (0 = conv1a .. 11 = convDb) exactly as the forward launches it
+    (``onepose_superpoint_layer``).  x is NHWC [B,h,w,cin] on the GPU ([B,h,w] for layer 0);
+    returns NHWC [B,h,w,cout], [B,h/2,w/2,cout] for the pooled layers 1, 3, 5, or the
+    pixel-shuffled score map [B,8h,8w] for layer 9."""
+    if x.device.type != "cuda":
+        raise RuntimeError("onepose_amd.superpoint runs on a ROCm GPU only")
+    lib = _lib.load()
+    if not 0 <= layer < len(LAYERS):
+        raise ValueError(f"layer {layer} not in [0, {len(LAYERS)})")
+    cout, cin, _ = SHAPES[LAYERS[layer]]
+    x = x.float().contiguous()
+    want = 3 if layer == 0 else 4
+    if x.dim() != want or (layer != 0 and x.shape[3] != cin):
+        raise ValueError(f"{LAYERS[layer]}: input {tuple(x.shape)} is not [B,h,w"
+                         + ("]" if layer == 0 else f",{cin}]"))
+    b, h, w = x.shape[:3]
+    if layer == 9:
+        shape = (b, 8 * h, 8 * w)
+    elif layer in POOLED_LAYERS:
+        shape = (b, h // 2, w // 2, cout)
+    else:
+        shape = (b, h, w, cout)
+    y = torch.empty(shape, dtype=torch.float32, device=x.device)
+    need = lib.onepose_superpoint_layer_out_floats(int(layer), h, w)
+    if need and y[0].numel() != need:   # (0: a size the entry point refuses, with its message)
+        raise _lib.OnePoseError("superpoint_layer: output size disagrees with the library")
+    _lib.check(lib.onepose_superpoint_layer(packed.data_ptr(), int(layer), x.data_ptr(), b, h, w,
+                                            y.data_ptr(), _lib.stream_ptr(x.device)),
+               "superpoint_layer")
+    return y
+
+
 def detect_from_maps(score_map, dense_nhwc, nms_radius=4, keypoint_threshold=0.005,
                      remove_borders=4, max_keypoints=-1, align_corners=None):
     """The detector's tail alone (simple_nms, threshold, remove_borders, top_k, flip,

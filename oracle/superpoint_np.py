@@ -26,8 +26,10 @@ LAYERS = ("conv1a", "conv1b", "conv2a", "conv2b", "conv3a", "conv3b", "conv4a", 
           "convPa", "convPb", "convDa", "convDb")
 
 
-def conv2d(x, w, b):
-    """nn.Conv2d(stride 1, padding k//2) on x [C,H,W]; w [O,C,k,k] -> [O,H,W] float32."""
+def conv2d_f64(x, w, b):
+    """nn.Conv2d(stride 1, padding k//2) on x [C,H,W]; w [O,C,k,k], in float64 and not
+    rounded.  Returns (y [O,H,W], abssum [O,H,W]) with abssum = |w| @ |cols| + |b|, the sum of
+    the magnitudes of every term of y: the scale of a floating-point summation's error bound."""
     c, h, wd = x.shape
     o, _, k, _ = w.shape
     p = k // 2
@@ -36,8 +38,16 @@ def conv2d(x, w, b):
     for dy in range(k):
         for dx in range(k):
             cols[:, dy, dx] = xp[:, dy:dy + h, dx:dx + wd]
-    y = w.reshape(o, -1).astype(np.float64) @ cols.reshape(c * k * k, h * wd)
-    return (y + b.astype(np.float64)[:, None]).astype(F32).reshape(o, h, wd)
+    cols = cols.reshape(c * k * k, h * wd)
+    w64, b64 = w.reshape(o, -1).astype(np.float64), b.astype(np.float64)[:, None]
+    y = w64 @ cols + b64
+    abssum = np.abs(w64) @ np.abs(cols) + np.abs(b64)
+    return y.reshape(o, h, wd), abssum.reshape(o, h, wd)
+
+
+def conv2d(x, w, b):
+    """conv2d_f64 rounded to float32: [O,H,W]."""
+    return conv2d_f64(x, w, b)[0].astype(F32)
 
 
 def _relu(x):

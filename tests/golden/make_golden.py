@@ -313,9 +313,20 @@ def superpoint_case():
     extract_features.py:19-24 on seeded synthetic weights and images; also the dense score map
     (after softmax + pixel shuffle, before NMS) and the normalised dense descriptors, computed
     with the reference module's own layers in its forward order."""
+    _superpoint_cases("superpoint", (("sq", 128, 128, 0, 4096), ("topk", 96, 160, 1, 300)))
+
+
+def superpoint_small_case():
+    """superpoint_case at frames that leave every convolution tile and the 32x32 NMS tile
+    partial: 40x56 (35 cells) with top-k 30, and the smallest legal frame, 16x16 (4 cells), with
+    max_keypoints -1 (every survivor, raster order)."""
+    _superpoint_cases("superpoint_small", (("k30", 40, 56, 2, 30), ("min", 16, 16, 3, -1)))
+
+
+def _superpoint_cases(name, cases):
     from src.models.extractors.SuperPoint.superpoint import SuperPoint
     out = {}
-    for tag, h, w, seed, max_kp in (("sq", 128, 128, 0, 4096), ("topk", 96, 160, 1, 300)):
+    for tag, h, w, seed, max_kp in cases:
         conf = dict(synthetic.SUPERPOINT_CONF, max_keypoints=max_kp)
         m = SuperPoint(conf).eval()
         sd = synthetic.superpoint_state_dict(seed)
@@ -340,7 +351,8 @@ def superpoint_case():
         out[f"{tag}_score_map"] = sc[0].numpy()
         out[f"{tag}_dense_desc"] = dd[0].numpy()
         out[f"{tag}_weights_sha"] = sha(*[sd[k] for k in sorted(sd)])
-    np.savez_compressed(os.path.join(HERE, "superpoint.npz"), **out)
+    np.savez_compressed(os.path.join(HERE, f"{name}.npz"), **out)
+    print(f"{name}:", {tag: len(out[f"{tag}_keypoints"]) for tag, *_ in cases})
 
 
 def main():
@@ -364,6 +376,7 @@ def main():
     eval_record_case()
     object_case()
     superpoint_case()
+    superpoint_small_case()
     anno3d_case()
 
 

@@ -18,7 +18,7 @@ float frand() {
 }  // namespace
 
 int main() {
-  if (onepose_abi_version() != 8) return 1;
+  if (onepose_abi_version() != 9) return 1;
   // matcher packer
   {
     const int n = onepose_matcher_num_tensors();
@@ -55,6 +55,33 @@ int main() {
     std::vector<unsigned char> packed(onepose_superpoint_packed_bytes());
     if (onepose_superpoint_pack(p.data(), n, packed.data()) != ONEPOSE_OK) return 5;
     std::printf("superpoint pack: %d tensors, %zu bytes\n", n, packed.size());
+    // the single-layer entry point refuses bad arguments before it launches anything
+    const void* pk = packed.data();
+    const float* x = t[0].data();
+    float* y = t[0].data();
+    if (onepose_superpoint_layer(nullptr, 0, x, 1, 2, 2, y, nullptr) != ONEPOSE_ERR_INVALID) return 11;
+    if (onepose_superpoint_layer(pk, 0, nullptr, 1, 2, 2, y, nullptr) != ONEPOSE_ERR_INVALID) return 11;
+    if (onepose_superpoint_layer(pk, 0, x, 1, 2, 2, nullptr, nullptr) != ONEPOSE_ERR_INVALID) return 11;
+    if (onepose_superpoint_layer(pk, -1, x, 1, 2, 2, y, nullptr) != ONEPOSE_ERR_INVALID) return 12;
+    if (onepose_superpoint_layer(pk, 12, x, 1, 2, 2, y, nullptr) != ONEPOSE_ERR_INVALID) return 12;
+    if (onepose_superpoint_layer(pk, 2, x, 1, 0, 2, y, nullptr) != ONEPOSE_ERR_INVALID) return 13;
+    if (onepose_superpoint_layer(pk, 2, x, 1, 2, -4, y, nullptr) != ONEPOSE_ERR_INVALID) return 13;
+    if (onepose_superpoint_layer(pk, 2, x, 0, 2, 2, y, nullptr) != ONEPOSE_ERR_INVALID) return 13;
+    if (onepose_superpoint_layer(pk, 2, x, 1, 4096, 2048, y, nullptr) != ONEPOSE_ERR_INVALID) return 13;
+    if (onepose_superpoint_layer(pk, 2, x, 1, 65536, 65536, y, nullptr) != ONEPOSE_ERR_INVALID) return 13;
+    for (int l : {1, 3, 5}) {   // the pooled layers need even sides
+      if (onepose_superpoint_layer(pk, l, x, 1, 3, 4, y, nullptr) != ONEPOSE_ERR_INVALID) return 14;
+      if (onepose_superpoint_layer(pk, l, x, 1, 4, 5, y, nullptr) != ONEPOSE_ERR_INVALID) return 14;
+    }
+    if (!onepose_last_error()[0]) return 15;
+    // output sizes: plain, pooled, score head; 0 for what the entry point refuses
+    if (onepose_superpoint_layer_out_floats(0, 3, 5) != 64u * 15) return 16;
+    if (onepose_superpoint_layer_out_floats(5, 4, 6) != 128u * 6) return 16;
+    if (onepose_superpoint_layer_out_floats(9, 3, 5) != 64u * 15) return 16;
+    if (onepose_superpoint_layer_out_floats(11, 2, 18) != 256u * 36) return 16;
+    if (onepose_superpoint_layer_out_floats(12, 2, 2) || onepose_superpoint_layer_out_floats(-1, 2, 2) ||
+        onepose_superpoint_layer_out_floats(3, 0, 2) || onepose_superpoint_layer_out_floats(3, 4096, 2048))
+      return 17;
   }
   // size queries
   const int shapes[][4] = {{1, 1, 1, 1},     {1, 256, 512, 8},  {2, 1024, 4096, 8},

@@ -19,7 +19,7 @@ float frand() {
 }  // namespace
 
 int main() {
-  if (onepose_abi_version() != 8 || onepose_superglue_version() != 1) return 1;
+  if (onepose_abi_version() != 9 || onepose_superglue_version() != 1) return 1;
   // packer: exactly-sized tensors, so a read past any of them is reported
   {
     const int n = onepose_superglue_num_tensors();

@@ -160,7 +160,7 @@ def test_cpu_forward_raises():
 
 def test_superglue_version(lib):
     assert lib.onepose_superglue_version() == 1 == superglue.SUPERGLUE_VERSION
-    assert lib.onepose_abi_version() == 8
+    assert lib.onepose_abi_version() == 9
 
 
 def _match(lib, precision=0, n0=5, n1=6, iters=10, ws=256, ws_bytes=1 << 40, batch=1):

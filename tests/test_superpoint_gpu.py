@@ -5,19 +5,23 @@ Bars: the detector tail (NMS, threshold, borders, top-k, flip) is integer/select
 must be bit-exact given the same score map; the convolutions are fp32 with a different
 summation order than the reference, so the score map is compared at rtol 1e-4 / atol 1e-6
 and the dense / sampled descriptors at atol 2e-5; the end-to-end keypoints of the golden
-cases must equal the reference's."""
+cases must equal the reference's.  The ragged frames (16x16 .. 56x88: 4 .. 77 cells of 8x8 pixels)
+leave the last tile of every convolution, and the 32x32 NMS tile, partial."""
 import numpy as np
 import pytest
 import torch
 
 from conftest import golden
-from onepose_amd import synthetic
+from onepose_amd import _lib, synthetic
 from onepose_amd.superpoint import SuperPoint, detect_from_maps
 from oracle import superpoint_np as O
 
 pytestmark = pytest.mark.gpu
 CASES = {"sq": (128, 128, 0, 4096), "topk": (96, 160, 1, 300)}
+SMALL = {"k30": (40, 56, 2, 30), "min": (16, 16, 3, -1)}     # tests/golden/superpoint_small.npz
 CONF = dict(nms_radius=3, keypoint_threshold=0.005, remove_borders=4)
+# c = h/8 * w/8 = 4, 6, 15, 25, 18, 18, 77 cells: no multiple of 4, 16 or 32 but the first
+RAGGED = [(16, 16), (16, 24), (24, 40), (40, 40), (16, 72), (72, 16), (56, 88)]
 
 
 def model(seed, max_kp, device, **kw):
@@ -203,3 +207,82 @@ def test_nms_radius_matches_oracle(radius, device):
     assert n == len(kp_o)
     np.testing.assert_array_equal(kp, kp_o)
     np.testing.assert_array_equal(sc, sc_o)
+
+
+@pytest.mark.parametrize("tag", sorted(SMALL))
+def test_end_to_end_matches_reference_small(tag, device):
+    """The reference's own outputs at 40x56 (top-k 30) and 16x16 (every survivor)."""
+    h, w, seed, max_kp = SMALL[tag]
+    g = golden("superpoint_small")
+    m = model(seed, max_kp, device)
+    img = torch.from_numpy(synthetic.superpoint_image(h, w, seed))[None, None].to(device)
+    raw = m.detect_raw(img, score_map=True, dense=True)
+    np.testing.assert_allclose(raw["score_map"][0].cpu().numpy(), g[f"{tag}_score_map"],
+                               rtol=1e-4, atol=1e-6)
+    np.testing.assert_allclose(raw["dense"][0].permute(2, 0, 1).cpu().numpy(),
+                               g[f"{tag}_dense_desc"], atol=2e-5)
+    kp, sc, desc, n = first(raw)
+    assert n == len(g[f"{tag}_keypoints"]) > 0
+    np.testing.assert_array_equal(kp, g[f"{tag}_keypoints"])
+    np.testing.assert_allclose(sc, g[f"{tag}_scores"], rtol=1e-4, atol=1e-7)
+    np.testing.assert_allclose(desc, g[f"{tag}_descriptors"], atol=2e-5)
+    # and the tail alone, bit-exact on the reference's maps
+    smap = torch.from_numpy(g[f"{tag}_score_map"])[None].to(device)
+    dense = torch.from_numpy(g[f"{tag}_dense_desc"]).permute(1, 2, 0)[None].contiguous().to(device)
+    kp, sc, desc, _ = first(detect_from_maps(smap, dense, max_keypoints=max_kp,
+                                             align_corners=False, **CONF))
+    np.testing.assert_array_equal(kp, g[f"{tag}_keypoints"])
+    np.testing.assert_array_equal(sc, g[f"{tag}_scores"])
+    np.testing.assert_allclose(desc, g[f"{tag}_descriptors"], atol=1e-6)
+
+
+@pytest.mark.parametrize("size", RAGGED, ids=lambda s: f"{s[0]}x{s[1]}")
+def test_ragged_frame_matches_oracle(size, device):
+    """Whole network at frames whose maps fill no tile: score map and dense descriptors against
+    the oracle, keypoints exactly the oracle tail on the GPU's own score map."""
+    h, w = size
+    seed = h + w
+    sd = synthetic.superpoint_state_dict(seed)
+    img = synthetic.superpoint_image(h, w, seed)
+    x = O.encoder(sd, img)
+    smap_o, dense_o = O.score_map(sd, x), O.dense_descriptors(sd, x)
+    for border in (0, 4):
+        m = model(seed, -1, device, remove_borders=border)
+        raw = m.detect_raw(torch.from_numpy(img)[None, None].to(device), score_map=True, dense=True)
+        smap = raw["score_map"][0].cpu().numpy()
+        dense = raw["dense"][0].permute(2, 0, 1).cpu().numpy()
+        np.testing.assert_allclose(smap, smap_o, rtol=1e-4, atol=1e-6)
+        np.testing.assert_allclose(dense, dense_o, atol=2e-5)
+        kp_o, sc_o = O.select_keypoints(O.simple_nms(smap, 3), 0.005, border, -1)
+        assert len(kp_o) >= 3
+        kp, sc, desc, n = first(raw)
+        assert n == len(kp_o)
+        np.testing.assert_array_equal(kp, kp_o)
+        np.testing.assert_array_equal(sc, sc_o)
+        d_o = O.sample_descriptors(kp_o[None], dense[None], 8, False)[0]
+        np.testing.assert_allclose(desc, d_o, atol=1e-6)
+        assert not raw["keypoints"][0, n:].any() and not raw["descriptors"][0, :, n:].any()
+
+
+@pytest.mark.parametrize("size", [(24, 40), (56, 88)], ids=lambda s: f"{s[0]}x{s[1]}")
+def test_ragged_batch_equals_single_images(size, device):
+    h, w = size
+    m = model(1, 20, device)
+    imgs = [synthetic.superpoint_image(h, w, s) for s in (7, 8, 9)]
+    batch = m.detect_raw(torch.from_numpy(np.stack(imgs))[:, None].to(device), score_map=True,
+                         dense=True)
+    for i, im in enumerate(imgs):
+        one = m.detect_raw(torch.from_numpy(im)[None, None].to(device), score_map=True, dense=True)
+        for key in ("score_map", "dense"):
+            np.testing.assert_array_equal(batch[key][i].cpu().numpy(), one[key][0].cpu().numpy())
+        assert int(one["counts"][0]) > 0
+        for a, b in zip(first(batch, i), first(one)):
+            np.testing.assert_array_equal(np.asarray(a), np.asarray(b))
+
+
+@pytest.mark.parametrize("size", [(8, 8), (8, 64)], ids=lambda s: f"{s[0]}x{s[1]}")
+def test_frames_below_16_are_refused(size, device):
+    """check_detect_args runs before the first launch: an error, and the outputs untouched."""
+    m = model(0, 64, device)
+    with pytest.raises(_lib.OnePoseError, match=">= 16"):
+        m.detect_raw(torch.zeros(1, 1, *size, device=device))

@@ -1,7 +1,9 @@
 """Pin the SuperPoint oracle (oracle/superpoint_np.py) to the reference module's own outputs
 (tests/golden/superpoint.npz: superpoint.py run on seeded weights and images in the build
 container, extraction config of extract_features.py:19-24 -> nms_radius 3, threshold 0.005,
-max_keypoints 4096 / 300)."""
+max_keypoints 4096 / 300), and to tests/golden/superpoint_small.npz, the same at frames off
+every tile grid: 40x56 with top-k 30 and the smallest legal frame, 16x16, with max_keypoints -1
+(make_golden.py superpoint_small_case)."""
 import hashlib
 
 import numpy as np
@@ -11,7 +13,10 @@ from conftest import golden
 from onepose_amd import synthetic
 from oracle import superpoint_np as O
 
-CASES = {"sq": (128, 128, 0, 4096), "topk": (96, 160, 1, 300)}
+CASES = {"sq": (128, 128, 0, 4096), "topk": (96, 160, 1, 300),
+         "k30": (40, 56, 2, 30), "min": (16, 16, 3, -1)}
+FIXTURE = {"sq": "superpoint", "topk": "superpoint", "k30": "superpoint_small",
+           "min": "superpoint_small"}
 
 
 def case(tag):
@@ -20,7 +25,7 @@ def case(tag):
     sha = hashlib.sha256()
     for k in sorted(sd):
         sha.update(np.ascontiguousarray(sd[k]).tobytes())
-    g = golden("superpoint")
+    g = golden(FIXTURE[tag])
     assert sha.hexdigest() == str(g[f"{tag}_weights_sha"]), "weight generator drifted"
     return sd, synthetic.superpoint_image(h, w, seed), max_kp, g
 
@@ -61,6 +66,16 @@ def test_topk_case_exercises_truncation():
     assert len(kp_all) > 300 and len(g["topk_keypoints"]) == 300
     s = g["topk_scores"]
     assert np.all(s[:-1] >= s[1:])
+
+
+def test_small_cases_take_both_selection_branches():
+    g = golden("superpoint_small")
+    kp_all, _ = O.select_keypoints(O.simple_nms(g["k30_score_map"], 3), 0.005, 4, -1)
+    assert len(kp_all) > 30 and len(g["k30_keypoints"]) == 30        # top-k, descending
+    assert np.all(g["k30_scores"][:-1] >= g["k30_scores"][1:])
+    kp = g["min_keypoints"]                                           # -1: raster order
+    assert len(kp) >= 3 and np.all(np.diff(kp[:, 1] * 16 + kp[:, 0]) > 0)
+    assert g["min_score_map"].shape == (16, 16) and g["k30_score_map"].shape == (40, 56)
 
 
 def test_simple_nms_keeps_plateau_and_isolated_maxima():
