@@ -557,6 +557,86 @@ int onepose_mha_softmax(const float* q, int64_t q_bstride, const float* k, int64
                         int64_t out_bstride, void* stream);
 
 /* ------------------------------------------------------------------------------------ *
+ * 2D object detector  --  replaces the arithmetic of LocalFeatureObjectDetector
+ *   (src/local_feature_2D_detector/local_feature_2D_detector.py: match_worker :77-133,
+ *    detect_by_matching :135-147, crop_img_by_bbox :160-186), the caller the SuperGlue family
+ *   above was built for: after the SuperGlue forwards of one query frame against the reference
+ *   views, the correspondence selection, cv2.estimateAffinePartial2D per view, the box of the
+ *   warped view corners, the choice of view and the two cv2.warpAffine crops.
+ * This family is versioned on its own, as the SuperGlue family: onepose_detector_version()
+ * returns 1; onepose_abi_version() was not bumped for it.
+ * OpenCV is restated after 4.4's ptsetreg.cpp / imgwarp.cpp from its published algorithm (no
+ * OpenCV here): parity with cv2 itself is pinned only by known-answer scenes.
+ * ------------------------------------------------------------------------------------ */
+int onepose_detector_version(void);
+/* cv2.estimateAffinePartial2D(from, to, method=RANSAC, ransacReprojThreshold=threshold,
+ * maxIters=max_iters, confidence, refineIters=refine_iters), one view per batch entry (one
+ * workgroup each, the view's points in LDS at 16 B per point): RANSACPointSetRegistrator with
+ * two-point subsets drawn from cv::RNG((uint64)-1), the minimal similarity in double, float32
+ * errors against (float)(threshold^2), RANSACUpdateNumIters, then Levenberg-Marquardt over the
+ * inliers (the mask is not recomputed).
+ *   from, to [batch, max_points, 2] fp32, counts [batch] int32 (clamped to [0, max_points]).
+ * Outputs: affine [batch, 6] fp64 row-major [a -b tx; b a ty] (zeros without an estimate),
+ * inlier_mask [batch, max_points] uint8, n_inliers [batch] int32, status [batch] int32:
+ *   0 = solved; 1 = fewer than 2 points; 2 = RANSAC found no model (every subset drawn had
+ *   coincident source points, or no model reached 2 inliers).
+ * Exactly 2 points: the minimal model of the two, both inliers, no refinement.
+ * onepose_affine_partial_max_points(): the largest max_points that fits the 160 KB of LDS (a
+ * host-side query); a larger one is refused with ONEPOSE_ERR_INVALID before anything is
+ * launched.  Workspace: onepose_affine_partial_workspace_bytes(batch, max_points); after the
+ * call its first `batch` int32 hold each view's number of RANSAC iterations run.
+ * All device pointers. */
+int onepose_affine_partial_max_points(void);
+size_t onepose_affine_partial_workspace_bytes(int batch, int max_points);
+int onepose_affine_partial_ransac(const float* from, const float* to, const int* counts,
+                                  int max_points, int batch, double threshold, int max_iters,
+                                  double confidence, int refine_iters, double* affine,
+                                  uint8_t* inlier_mask, int* n_inliers, int* status,
+                                  void* workspace, size_t workspace_bytes, void* stream);
+/* match_worker + detect_by_matching for one query frame, in one launch per frame plus one
+ * small ranking launch.  View b: matches0 [batch, n0] int64 (SuperGlue's, view keypoint ->
+ * query keypoint, -1 = none), of which the first counts0[b] are read (counts0 null: all n0);
+ * kpts0 [batch, n0, 2] the views' keypoints, kpts1 [n1, 2] the query's (kpts1_bstride
+ * elements between views, 0 = one shared query); db_hw [batch, 2] int32 the views' (h, w);
+ * query_h, query_w the query's.  The valid matches (matches0 > -1 and < n1) are compacted in
+ * ascending index order inside the RANSAC kernel, (from, to) = (view, query) points.
+ * Per view: counts [batch] the number of matches; mpts [batch, n0, 4] (x, y, X, Y) the compacted
+ * correspondences (may be null); affine / inlier_mask [batch, n0] / n_inliers as above; status 0
+ * = solved, 1 = fewer than 6 matches, 2 = no model; bbox [batch, 4] int32 (x0, y0, x1, y1) =
+ * min / max of the view's corners (0,0), (w,0), (0,h), (w,h) through affine in double, each
+ * truncated toward zero (astype(np.int32); a corner beyond int32 saturates here, where numpy
+ * wraps -- no real view gets there).  Without an estimate (status 1 or 2) the box is the
+ * reference's fallback [0, 0, query_h, query_w] -- its x1 is the height, as in the reference
+ * (:98) -- and n_inliers 0; the reference would raise on status 2 (affine is None).
+ * rank_mode 0 ranks a view by its number of matches (the reference: inliers.shape[0] of
+ * OpenCV's N x 1 mask), 1 by its number of inliers; a view without an estimate ranks 0; the
+ * first view in input order with the largest value wins (sorted(reverse=True) is stable):
+ * best_view [1], best_bbox [4] int32.  n0 <= onepose_affine_partial_max_points(); workspace:
+ * onepose_affine_partial_workspace_bytes(batch, n0).  All device pointers. */
+int onepose_detect_stage(const int64_t* matches0, const int* counts0, const float* kpts0,
+                         const float* kpts1, int64_t kpts1_bstride, const int* db_hw, int batch,
+                         int n0, int n1, int query_h, int query_w, double threshold,
+                         int max_iters, double confidence, int refine_iters, int rank_mode,
+                         int* counts, float* mpts, double* affine, uint8_t* inlier_mask,
+                         int* n_inliers, int* status, int* bbox, int* best_view, int* best_bbox,
+                         void* workspace, size_t workspace_bytes, void* stream);
+/* crop_img_by_bbox: image [h][w] uint8, bbox [4] int32 (x0, y0, x1, y1; a device pointer, e.g.
+ * best_bbox), K [9] fp64 or null -> crop_u8 [crop_size][crop_size], crop_f32 = crop_u8 / 255
+ * (may be null), K_crop [9] fp64 (null with K), crop_status [1] int32.  With bw = x1 - x0,
+ * bh = y1 - y0 the reference's two warps (get_affine_transform with rot 0, read in closed form)
+ * are T1 = [1 0 -x0; 0 1 -y0], an exact integer crop zero-filled outside the image, and T2 =
+ * [s 0 tx; 0 s ty] with s = crop_size / bw in BOTH axes (data_utils.py:34 reads src_w only),
+ * tx = crop_size/2 - s bw/2, ty = crop_size/2 - s bh/2: one bilinear warp of the zero-padded
+ * bw x bh window in cv2.warpAffine's fixed-point arithmetic (1/1024 coordinate steps, 5
+ * fractional bits, weights summing to 2^15), so the output is exact.  K_crop = T2 T1 K.
+ * bw <= 0 or bh <= 0: crop_status 1, a zero image, K_crop = K (the reference would raise).
+ * A box coordinate with |v| >= 2^15 (outside warpAffine's short maps; the integer walk would
+ * leave int range): crop_status 2, a zero image, K_crop = K.  Else crop_status 0. */
+int onepose_crop_resize(const uint8_t* image, int h, int w, const int* bbox, const double* K,
+                        int crop_size, uint8_t* crop_u8, float* crop_f32, double* K_crop,
+                        int* crop_status, void* stream);
+
+/* ------------------------------------------------------------------------------------ *
  * Measurement hook (bench.py's roofline). While enabled, every launch whose kernel kind
  * is in `kind_mask` (bit k = kind k, names from onepose_profile_kind_name) is bracketed by
  * two HIP events recorded on the launch's own stream.  Host-side state, not for use during

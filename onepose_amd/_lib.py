@@ -151,6 +151,21 @@ PROTOTYPES = {
                                               c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
     "onepose_mha_softmax": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64,
                                     c_int, c_int, c_int, c_void_p, c_int64, c_void_p]),
+    "onepose_detector_version": (c_int, []),
+    "onepose_affine_partial_max_points": (c_int, []),
+    "onepose_affine_partial_workspace_bytes": (c_size_t, [c_int, c_int]),
+    "onepose_affine_partial_ransac": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int,
+                                              c_double, c_int, c_double, c_int,
+                                              c_void_p, c_void_p, c_void_p, c_void_p,
+                                              c_void_p, c_size_t, c_void_p]),
+    "onepose_detect_stage": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p,
+                                     c_int, c_int, c_int, c_int, c_int,
+                                     c_double, c_int, c_double, c_int, c_int,
+                                     c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                     c_void_p, c_void_p, c_void_p,
+                                     c_void_p, c_size_t, c_void_p]),
+    "onepose_crop_resize": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_int,
+                                    c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "onepose_profile_begin": (c_int, [ctypes.c_uint64, c_int]),
     "onepose_profile_begin_device": (c_int, [ctypes.c_uint64]),
     "onepose_profile_end_device": (c_int, [c_void_p, c_void_p, c_int]),

@@ -15,6 +15,7 @@
 // inlier mask and the iteration count are those of the sequential algorithm.  The final
 // pose is a workgroup-parallel EPnP over the inliers.
 #include "common.h"
+#include "cv_rng.h"
 
 // The pose kernels are compiled for one wave per SIMD (amdgpu_waves_per_eu(1)): a wave may use
 // a whole SIMD's register file. 2 and 4 were measured slower or equal.
@@ -27,28 +28,11 @@ namespace {
 constexpr int kModelPoints = 5;
 constexpr int kRound = 64;
 constexpr int kThreads = 256;
-// cv::RNG (multiply-with-carry): state' = (state & 0xffffffff) * kMwcA + (state >> 32)
-constexpr unsigned long long kMwcA = 4164903690ull;
-constexpr unsigned long long kMwcM = kMwcA * 4294967296ull - 1ull;   // < 2^64
+// cv::RNG, its jump-ahead and RANSACUpdateNumIters: cv_rng.h (shared with detector.hip)
 constexpr int kRngPrefix = 8, kRngPos = kRngPrefix + 6 * 64;   // draws generated per round
 
 // A^(6 l) mod kMwcM, l = 0..63 (compile time)
-constexpr unsigned long long mwc_mulmod_c(unsigned long long a, unsigned long long b) {
-  return (unsigned long long)((unsigned __int128)a * b % kMwcM);
-}
-struct MwcJumps {
-  unsigned long long v[64];
-  constexpr MwcJumps() : v() {
-    unsigned long long a6 = 1ull;
-    for (int i = 0; i < 6; ++i) a6 = mwc_mulmod_c(a6, kMwcA);
-    unsigned long long x = 1ull;
-    for (int l = 0; l < 64; ++l) {
-      v[l] = x;
-      x = mwc_mulmod_c(x, a6);
-    }
-  }
-};
-__constant__ const MwcJumps kMwcJumps = MwcJumps();
+__constant__ const MwcJumps<6> kMwcJumps = MwcJumps<6>();
 
 // ---------------------------------------------------------------------------------------
 // small dense linear algebra, double
@@ -913,18 +897,6 @@ __device__ __forceinline__ void epnp5_approx(int which, const volatile int* sub,
   *err_out = err / n;
 }
 
-// RANSACUpdateNumIters (ptsetreg.cpp)
-__device__ __forceinline__ int update_num_iters(double p, double ep, int model_points, int max_iters) {
-  p = fmin(fmax(p, 0.0), 1.0);
-  ep = fmin(fmax(ep, 0.0), 1.0);
-  double num = fmax(1. - p, 2.2250738585072014e-308);
-  double denom = 1. - pow(1. - ep, (double)model_points);
-  if (denom < 2.2250738585072014e-308) return 0;
-  num = log(num);
-  denom = log(denom);
-  return (denom >= 0 || -num >= max_iters * (-denom)) ? max_iters : __double2int_rn(num / denom);
-}
-
 // squared float reprojection error of one point (computeError; no fp contraction)
 __device__ __forceinline__ float reproj_err2(const double* R, const double* t, const double* K4,
                                              float X, float Y, float Z, float u, float v) {
@@ -1585,27 +1557,6 @@ __device__ int p3p_solutions(const float* p2, const float* p3, const double* K4)
     ++sols;
   }
   return sols;
-}
-
-__device__ __forceinline__ unsigned rng_next(unsigned long long& s) {
-  s = (unsigned long long)(unsigned)s * 4164903690ull + (unsigned)(s >> 32);
-  return (unsigned)s;
-}
-
-// cv::RNG is a lag-1 multiply-with-carry generator: for a state z = c * 2^32 + x below
-// m = A * 2^32 - 1, the next state A x + c equals A z mod m (A 2^32 = 1 mod m), so the state
-// k draws ahead is A^k z mod m -- lane l of a wave starts its 6 draws at A^(6 l) z.
-__device__ __forceinline__ unsigned long long mwc_mulmod(unsigned long long a,
-                                                         unsigned long long b) {
-  // a b mod m for a, b < m: fold the high word with 2^64 = r (mod m), r = (2^32 - A) 2^32 + 1
-  constexpr unsigned long long r = ((4294967296ull - kMwcA) << 32) | 1ull;
-  unsigned long long lo = a * b, hi = __umul64hi(a, b);
-  while (hi != 0ull) {
-    const unsigned long long l2 = hi * r, h2 = __umul64hi(hi, r);
-    lo += l2;
-    hi = h2 + (lo < l2 ? 1ull : 0ull);
-  }
-  return lo >= kMwcM ? lo - kMwcM : lo;
 }
 
 // Correspondence selection fused into the RANSAC kernel (onepose_pose_stage): the frame's

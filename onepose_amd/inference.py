@@ -13,7 +13,11 @@ object: a Hydra ``DictConfig``, ``types.SimpleNamespace``; Hydra itself is out o
   checkpoint) and ``cfg.model.extractor_model_path`` (SuperPoint weights),
   ``cfg.network.detection``;
 * ``get_default_paths(cfg, data_root, data_dir, sfm_model_dir)`` (``:17-46``),
-  ``pack_data(...)`` (``:80-94``), ``cfg.num_leaf``, ``cfg.object_detect_mode``.
+  ``pack_data(...)`` (``:80-94``), ``cfg.num_leaf``, ``cfg.object_detect_mode``;
+* ``run_object_detector(seq_dir, extractor, matcher, ...)``
+  (``feature_matching_object_detector.py:117-148``): the 2D object detector over a sequence's
+  ``color_full/`` frames, writing the ``color_det/`` and ``intrin_det/`` directories that
+  ``object_detect_mode="feature_matching"`` reads.
 
 What changes against the reference loop:
 
@@ -91,7 +95,8 @@ def default_paths(data_dir: str, sfm_model_dir: str, detection: str = "superpoin
         color_dir = os.path.join(data_dir, "color_det")
         if not os.path.exists(color_dir):
             raise FileNotFoundError("color_det directory not found: run the 2D object detector "
-                                    "first (reference README)")
+                                    "first (onepose_amd.inference.run_object_detector; "
+                                    "reference README)")
     else:
         raise NotImplementedError(object_detect_mode)
     img_lists = sorted(glob.glob(color_dir + "/*.png"))
@@ -221,6 +226,56 @@ def inference_core_with_models(matcher: GATsSuperGlue, extractor, seq_dir: str,
         p, _, _, *_ = match_and_pose(matcher, obj, det["keypoints"], det["descriptors"], K)
         ev.evaluate(p, np.loadtxt(get_gt_pose_path_by_color(img_path, object_detect_mode)))
     return ev.summarize()
+
+
+def get_K(intrin_file: str):
+    """data_utils.get_K (:282-301): ``intrinsics.txt``'s four ``name: value`` lines (fx, fy, cx,
+    cy) -> (K [3,3], K_homo [3,4])."""
+    with open(intrin_file) as f:
+        fx, fy, cx, cy = (float(line.rstrip("\n").split(":")[1]) for line in f.readlines()[:4])
+    K = np.array([[fx, 0, cx], [0, fy, cy], [0, 0, 1]], np.float64)
+    return K, np.concatenate([K, np.zeros((3, 1))], 1)
+
+
+@torch.no_grad()
+def run_object_detector(seq_dir: str, extractor, matcher, db_dict=None, ref_images=None,
+                        n_ref_view: int = 15, K=None, crop_size: int = 512,
+                        rank_by: str = "reference", device="cuda"):
+    """``feature_matching_object_detector.inference_core`` (:117-148) for one sequence over
+    already-built models: every ``<seq_dir>/color_full/*.png`` goes through
+    ``LocalFeatureObjectDetector.detect``, which writes ``color_det/<name>.png`` (the crop) and
+    ``intrin_det/<name>.txt`` (K_crop) -- what ``object_detect_mode="feature_matching"`` reads.
+    Both directories are emptied first, as the reference does.  The reference views come from
+    ``db_dict`` or from ``ref_images`` (``detector.reference_views``; the reference reads them
+    from the object's COLMAP model, which is out of scope).  ``K``: the full image's intrinsics,
+    by default ``<seq_dir>/intrinsics.txt``.  Returns ``[(image path, bbox)]``."""
+    import shutil
+    from .detector import LocalFeatureObjectDetector, reference_views
+    color_dir = os.path.join(seq_dir, "color_full")
+    if not os.path.exists(color_dir):
+        raise FileNotFoundError(f"{color_dir} not found (extracting Frames.m4v is out of scope)")
+    img_lists = sorted(glob.glob(color_dir + "/*.png"))
+    det_dir, K_dir = os.path.join(seq_dir, "color_det"), os.path.join(seq_dir, "intrin_det")
+    for d in (det_dir, K_dir):
+        if os.path.exists(d):
+            shutil.rmtree(d)
+        os.makedirs(d)
+    if K is None:
+        K, _ = get_K(os.path.join(seq_dir, "intrinsics.txt"))
+    if db_dict is None:
+        if ref_images is None:
+            raise ValueError("run_object_detector needs db_dict or ref_images")
+        db_dict = reference_views(ref_images, extractor, n_ref_view)
+    detector = LocalFeatureObjectDetector(extractor, matcher, db_dict=db_dict,
+                                          n_ref_view=n_ref_view, output_results=True,
+                                          detect_save_dir=det_dir, K_crop_save_dir=K_dir,
+                                          rank_by=rank_by, device=device)
+    out = []
+    for img_path in img_lists:
+        img, _ = load_image(img_path)
+        bbox, _, _ = detector.detect(torch.from_numpy(img)[None], img_path, K, crop_size)
+        out.append((img_path, bbox))
+    return out
 
 
 def seed_reference_stream(seed: int = REFERENCE_SEED):
