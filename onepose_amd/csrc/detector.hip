@@ -5,7 +5,7 @@
 //   * crop_img_by_bbox as one integer bilinear warp.
 //
 // RANSAC, per round of 64 iterations of OpenCV's loop:
-//   1. wave 0 generates the round's cv::RNG draws by jump-ahead (cv_rng.h), thread 0 deals the
+//   1. wave 0 generates the round's cv::RNG draws by jump-ahead (ransac.h), thread 0 deals the
 //      64 two-point subsets from them in iteration order (a duplicate index is redrawn, so a
 //      subset takes a varying number of draws; a chain that outruns the generated draws goes
 //      on sequentially);
@@ -17,7 +17,7 @@
 // iteration count are those of the sequential loop.  Wave 0 then refines the model over the
 // inliers (Levenberg-Marquardt in the shape of LMSolverImpl::run).
 #include "common.h"
-#include "cv_rng.h"
+#include "ransac.h"
 
 namespace onepose {
 namespace {
@@ -25,24 +25,17 @@ namespace {
 constexpr int kModelPoints = 2;
 constexpr int kRound = 64;
 constexpr int kThreads = 256;
-constexpr int kDrawsPerLane = 4;
-constexpr int kRngPrefix = 8, kRngPos = kRngPrefix + kDrawsPerLane * 64;   // draws per round
-constexpr int kMinMatches = 6;   // local_feature_2D_detector.py:93
-
-__constant__ const MwcJumps<kDrawsPerLane> kDetJumps = MwcJumps<kDrawsPerLane>();
+constexpr int kDrawsPerLane = 4;   // generated per round: 8 + 4 * 64 draws
+constexpr int kMinMatches = 6;     // local_feature_2D_detector.py:93
 
 struct Shared {
-  unsigned long long rst[kRngPos];   // state after each generated draw
-  int rii[kRngPos];                  // draw % n
+  RansacDraws<kDrawsPerLane> draws;
   int subset[kRound][kModelPoints];
   double hyp[kRound][4];             // S0..S3 of each hypothesis
   int count[kRound];
-  unsigned long long rng, rz;
-  int rk, rP;
-  int iter, niters, max_good, done;
+  RansacCtl ctl;
   double best[4];
   int wave_cnt[4];
-  int n_inl;
   double h[4];                       // refined [a, b, tx, ty]
 };
 
@@ -77,22 +70,6 @@ __device__ __forceinline__ void model_to_float(const double* S, float* F) {
   F[3] = (float)S[1];
   F[4] = (float)S[0];
   F[5] = (float)S[3];
-}
-
-__device__ __forceinline__ double wave_sum_d(double v) {
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-__device__ __forceinline__ double wave_max_d(double v) {
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) v = fmax(v, __shfl_xor(v, o, 64));
-  return v;
-}
-__device__ __forceinline__ void wave_lds_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
 // Correspondence selection fused into the kernel (onepose_detect_stage): view b's valid matches
@@ -137,13 +114,8 @@ void affine_ransac_kernel(const float* __restrict__ from, const float* __restric
       const int i = start + t;
       const int64_t j = (i < nk) ? m[i] : -1;
       const bool valid = j > -1 && j < sel.n1;
-      const unsigned long long bal = __ballot(valid);
-      if (lane == 0) sh.wave_cnt[wave] = __popcll(bal);
-      __syncthreads();
-      int off = base;
-      for (int w2 = 0; w2 < wave; ++w2) off += sh.wave_cnt[w2];
+      const int q = compact_step<4>(valid, sh.wave_cnt, base);
       if (valid) {
-        const int q = off + __popcll(bal & ((1ull << lane) - 1ull));
         const float4 p = make_float4(k0[(int64_t)i * 2], k0[(int64_t)i * 2 + 1], k1[j * 2],
                                      k1[j * 2 + 1]);
         pts[q] = p;
@@ -154,8 +126,6 @@ void affine_ransac_kernel(const float* __restrict__ from, const float* __restric
           mo[4 * q + 3] = p.w;
         }
       }
-      base += sh.wave_cnt[0] + sh.wave_cnt[1] + sh.wave_cnt[2] + sh.wave_cnt[3];
-      __syncthreads();
     }
     n = base;
     if (t == 0) sel.counts[b] = n;
@@ -193,13 +163,7 @@ void affine_ransac_kernel(const float* __restrict__ from, const float* __restric
     }
   }
   const float thr = (float)(threshold * threshold);
-  if (t == 0) {
-    sh.iter = 0;
-    sh.niters = max(max_iters, 1);
-    sh.max_good = 0;
-    sh.done = (n == kModelPoints) ? 1 : 0;
-    sh.rng = 0xFFFFFFFFFFFFFFFFull;
-  }
+  if (t == 0) ransac_ctl_init(sh.ctl, max_iters, n == kModelPoints);
   __syncthreads();
 
   if (n == kModelPoints) {   // the kernel once on both points; all points are inliers
@@ -219,44 +183,18 @@ void affine_ransac_kernel(const float* __restrict__ from, const float* __restric
     return;   // (the stage never gets here: it needs 6 matches)
   }
 
-  while (!sh.done) {
-    // the round's draws, in parallel by jump-ahead (states at or above m -- the first draws
-    // from RNG((uint64)-1) -- are stepped by lane 0 first)
+  while (!sh.ctl.done) {
     if (wave == 0) {
-      if (lane == 0) {
-        unsigned long long z = sh.rng;
-        int k = 0;
-        while (z >= kMwcM && k < kRngPrefix) {
-          const unsigned v = rng_next(z);
-          sh.rst[k] = z;
-          sh.rii[k] = (int)(v % (unsigned)n);
-          ++k;
-        }
-        sh.rk = k;
-        sh.rz = z;
-      }
-      wave_lds_sync();
-      const int k = sh.rk;
-      const unsigned long long z0 = sh.rz;
-      if (z0 < kMwcM) {
-        unsigned long long z = mwc_mulmod(z0, kDetJumps.v[lane]);
-#pragma unroll
-        for (int i = 0; i < kDrawsPerLane; ++i) {
-          const unsigned v = rng_next(z);
-          sh.rst[k + kDrawsPerLane * lane + i] = z;
-          sh.rii[k + kDrawsPerLane * lane + i] = (int)(v % (unsigned)n);
-        }
-      }
+      const int P = ransac_round_draws(sh.draws, sh.ctl, n);   // the round's draws, in parallel
       wave_lds_sync();
       if (lane == 0) {   // getSubset x 64 in iteration order
-        const int P = z0 < kMwcM ? k + kDrawsPerLane * 64 : k;
-        unsigned long long st = sh.rng;
+        unsigned long long st = sh.ctl.rng;
         int pos = 0;
         auto draw = [&]() {
           int v;
           if (pos < P) {
-            st = sh.rst[pos];
-            v = sh.rii[pos];
+            st = sh.draws.rst[pos];
+            v = sh.draws.rii[pos];
           } else {
             v = (int)(rng_next(st) % (unsigned)n);
           }
@@ -270,7 +208,7 @@ void affine_ransac_kernel(const float* __restrict__ from, const float* __restric
           sh.subset[h][0] = i0;
           sh.subset[h][1] = i1;
         }
-        sh.rng = st;
+        sh.ctl.rng = st;
       }
       wave_lds_sync();
       double S[4];
@@ -283,47 +221,32 @@ void affine_ransac_kernel(const float* __restrict__ from, const float* __restric
     for (int h = wave; h < kRound; h += 4) {
       float F[6];
       model_to_float(sh.hyp[h], F);
-      int c = 0;
-      for (int i = lane; i < n; i += 64) c += affine_err2(F, pts[i]) <= thr;
-#pragma unroll
-      for (int o = 32; o >= 1; o >>= 1) c += __shfl_xor(c, o, 64);
+      const int c =
+          wave_count_if(lane, n, 64, [&](int i) { return affine_err2(F, pts[i]) <= thr; });
       if (lane == 0) sh.count[h] = c;
     }
     __syncthreads();
     if (t == 0) {   // the acceptance rule, in iteration order
-      int iter = sh.iter, niters = sh.niters, best = sh.max_good;
-      for (int h = 0; h < kRound && iter < niters; ++h, ++iter) {
-        const int good = sh.count[h];
-        if (good > max(best, kModelPoints - 1)) {
-          best = good;
-          for (int i = 0; i < 4; ++i) sh.best[i] = sh.hyp[h][i];
-          niters = update_num_iters(confidence, (double)(n - good) / n, kModelPoints, niters);
-        }
-      }
-      sh.iter = iter;
-      sh.niters = niters;
-      sh.max_good = best;
-      sh.done = iter >= niters;
+      ransac_accept(sh.ctl, sh.count, 0, kRound, n, confidence, kModelPoints, [&](int h) {
+        for (int i = 0; i < 4; ++i) sh.best[i] = sh.hyp[h][i];
+      });
     }
     __syncthreads();
   }
 
-  if (t == 0) iters_run[b] = sh.iter;
-  if (sh.max_good <= 0) {
+  if (t == 0) iters_run[b] = sh.ctl.iter;
+  if (sh.ctl.max_good <= 0) {
     none(2);
     return;
   }
   // the best model's mask
   float F[6];
   model_to_float(sh.best, F);
-  int c = 0;
-  for (int i = t; i < n; i += kThreads) {
+  const int c = wave_count_if(t, n, kThreads, [&](int i) {
     const bool in = affine_err2(F, pts[i]) <= thr;
     mask[i] = in ? 1 : 0;
-    c += in;
-  }
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) c += __shfl_xor(c, o, 64);
+    return in;
+  });
   if (lane == 0) sh.wave_cnt[wave] = c;
   __syncthreads();
   const int nin = sh.wave_cnt[0] + sh.wave_cnt[1] + sh.wave_cnt[2] + sh.wave_cnt[3];

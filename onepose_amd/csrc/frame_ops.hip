@@ -5,6 +5,7 @@
 //     eval_utils.py:22-26)
 //   * cm/deg pose error (eval_utils.py:45-63, cmd_evaluator.py:11-31)
 #include "common.h"
+#include "ransac.h"   // compact_step
 
 namespace onepose {
 
@@ -88,43 +89,28 @@ __global__ __launch_bounds__(1024) void select_kernel(const int64_t* __restrict_
                                                       float* __restrict__ p3,
                                                       int* __restrict__ counts) {
   __shared__ int wave_tot[16];
-  __shared__ int base_s;
   const int b = blockIdx.x;
-  const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+  const int t = threadIdx.x;
   const int64_t* m = matches0 + (int64_t)b * n1;
   const float* k2 = kp2 + b * kp2_bs;
   const float* k3 = kp3 + b * kp3_bs;
   float* o2 = p2 + (int64_t)b * n1 * 2;
   float* o3 = p3 + (int64_t)b * n1 * 3;
-  if (t == 0) base_s = 0;
-  __syncthreads();
+  int base = 0;
   for (int start = 0; start < n1; start += 1024) {
     const int i = start + t;
     int64_t j = (i < n1) ? m[i] : -1;
     const bool valid = j > -1 && j < n3;
-    const unsigned long long bal = __ballot(valid);
-    const int before = __popcll(bal & ((1ull << lane) - 1ull));
-    if (lane == 0) wave_tot[wave] = __popcll(bal);
-    __syncthreads();
-    int off = base_s;
-    for (int w2 = 0; w2 < wave; ++w2) off += wave_tot[w2];
+    const int pos = compact_step<16>(valid, wave_tot, base);
     if (valid) {
-      const int pos = off + before;
       o2[pos * 2 + 0] = k2[(int64_t)i * 2 + 0];
       o2[pos * 2 + 1] = k2[(int64_t)i * 2 + 1];
       o3[pos * 3 + 0] = (float)((double)k3[j * 3 + 0] * scale);
       o3[pos * 3 + 1] = (float)((double)k3[j * 3 + 1] * scale);
       o3[pos * 3 + 2] = (float)((double)k3[j * 3 + 2] * scale);
     }
-    __syncthreads();
-    if (t == 0) {
-      int tot = 0;
-      for (int w2 = 0; w2 < 16; ++w2) tot += wave_tot[w2];
-      base_s += tot;
-    }
-    __syncthreads();
   }
-  if (t == 0) counts[b] = base_s;
+  if (t == 0) counts[b] = base;
 }
 
 // query_pose_error / Evaluator (pose_error_one, common.h), one thread per frame.

@@ -2,20 +2,26 @@
 // it (see include/onepose_hip.h and oracle/epnp_ransac.c for the algorithm statement),
 // one workgroup per frame.
 //
-// Per RANSAC round the workgroup takes the next 64 iterations of OpenCV's loop:
-//   1. lane 0 draws the 64 subsets from the cv::RNG stream (sequential by definition:
-//      duplicate indices are redrawn);
-//   2. wave 0 solves one 5-point EPnP per lane (rvec, tvec);
-//   3. all 256 threads count inliers of the 64 models over the frame's points (float32
-//      squared reprojection error <= thr^2, as PnPRansacCallback::computeError);
-//   4. lane 0 replays OpenCV's acceptance rule in iteration order (goodCount >
-//      max(best, 4) -> new best, niters = RANSACUpdateNumIters(...)) and stops the loop
-//      exactly where OpenCV would.
+// pnp_ransac_kernel keeps the frame's points in LDS (compacted there from the matches when
+// the call is onepose_pose_stage) and per round takes the next 64 iterations of OpenCV's loop
+// (the scaffold -- draws, inlier count, acceptance, compaction -- is ransac.h's):
+//   1. wave 0 generates the round's cv::RNG draws by jump-ahead; a subset takes draws until it
+//      has 5 distinct indices, so every thread finds where a subset starting at its draws
+//      would end, thread 0 chains the 64 starts, and lane h deals subset h (a chain that
+//      outruns the generated draws goes on sequentially);
+//   2. one 5-point EPnP per hypothesis: wave 0 the eigenvectors (lane h = hypothesis h), waves
+//      1-3 one of the three approximations each; the smallest mean error wins (rvec, tvec);
+//   3. 16 iterations at a time, each wave counts the inliers of its hypotheses over the
+//      frame's points (float32 squared reprojection error <= thr^2, as
+//      PnPRansacCallback::computeError) and thread 0 replays OpenCV's acceptance rule in
+//      iteration order (goodCount > max(best, 4) -> new best, niters =
+//      RANSACUpdateNumIters(...)), stopping the loop exactly where OpenCV would.
 // Iterations evaluated beyond the stopping point are discarded, so the chosen model, the
-// inlier mask and the iteration count are those of the sequential algorithm.  The final
-// pose is a workgroup-parallel EPnP over the inliers.
+// inlier mask and the iteration count are those of the sequential algorithm.  The kernel ends
+// with the best model's inliers compacted in point order; pnp_refit_kernel computes the final
+// pose from them, a workgroup-parallel EPnP.
 #include "common.h"
-#include "cv_rng.h"
+#include "ransac.h"
 
 // The pose kernels are compiled for one wave per SIMD (amdgpu_waves_per_eu(1)): a wave may use
 // a whole SIMD's register file. 2 and 4 were measured slower or equal.
@@ -28,11 +34,8 @@ namespace {
 constexpr int kModelPoints = 5;
 constexpr int kRound = 64;
 constexpr int kThreads = 256;
-// cv::RNG, its jump-ahead and RANSACUpdateNumIters: cv_rng.h (shared with detector.hip)
-constexpr int kRngPrefix = 8, kRngPos = kRngPrefix + 6 * 64;   // draws generated per round
-
-// A^(6 l) mod kMwcM, l = 0..63 (compile time)
-__constant__ const MwcJumps<6> kMwcJumps = MwcJumps<6>();
+constexpr int kDrawsPerLane = 6;   // generated per round: 8 + 6 * 64 draws
+constexpr int kRngPos = RansacDraws<kDrawsPerLane>::kPos;
 
 // ---------------------------------------------------------------------------------------
 // small dense linear algebra, double
@@ -914,12 +917,6 @@ __device__ __forceinline__ float reproj_err2(const double* R, const double* t, c
 // ---------------------------------------------------------------------------------------
 // workgroup reductions (double)
 // ---------------------------------------------------------------------------------------
-__device__ __forceinline__ double wave_sum_d(double v) {
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
 // sum `cnt` per-thread values across the workgroup; every thread gets the totals
 template <int CNT>
 __device__ __forceinline__ void block_sum(double* vals, double* scratch /* [4][CNT] */) {
@@ -946,16 +943,14 @@ struct Shared {
   double hypT[kRound][3];
   double hypRvec[kRound][3];
   int count[kRound];
-  // RNG positions of a round, generated in parallel: state after each draw, draw % n
-  unsigned long long rst[kRngPos];
-  int rii[kRngPos];
+  // a round's draws, generated in parallel, and the chain of subset starts through them
+  RansacDraws<kDrawsPerLane> draws;
   short rend[kRngPos], rstart[kRound];
-  unsigned long long rz;
-  int rk, rP, rdealt, rpos;
+  int rdealt, rpos;
   // control
-  int iter, niters, max_good, done, p3p;
+  RansacCtl ctl;
+  int p3p;
   double bestRvec[3], bestT[3];
-  unsigned long long rng;
   // refit
   double red[4 * 78];
   double cws[4][3];
@@ -970,7 +965,7 @@ struct Shared {
   double S40[40];                    // M^T M's distinct sums (refit, n >= 6)
   int ord[4];
   int wave_cnt[4];
-  int n_inl;
+  int spare_[2];   // sizeof(Shared) sets onepose_pnp_max_points(): kept at its published 5297
   // refit eigensolver (jacobi12_wave)
   double jA[144], jV[144];
 };
@@ -988,11 +983,6 @@ struct Shared {
 // paid three of per round.  EPnP's result does not depend on the eigenvectors' signs, and
 // any accurate eigensolver gives the oracle's vectors up to sign when the eigenvalues are
 // separated.
-__device__ __forceinline__ void wave_lds_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
 __device__ __forceinline__ void jacobi_rot(double app, double aqq, double apq, double& c, double& sn) {
   c = 1.0;
   sn = 0.0;
@@ -1598,13 +1588,8 @@ void pnp_ransac_kernel(
       const int i = start + t;
       const int64_t j = (i < sel.n1) ? m[i] : -1;
       const bool valid = j > -1 && j < sel.n3;
-      const unsigned long long bal = __ballot(valid);
-      if (lane == 0) sh.wave_cnt[wave] = __popcll(bal);
-      __syncthreads();
-      int off = base;
-      for (int w2 = 0; w2 < wave; ++w2) off += sh.wave_cnt[w2];
+      const int q = compact_step<4>(valid, sh.wave_cnt, base);
       if (valid) {
-        const int q = off + __popcll(bal & ((1ull << lane) - 1ull));
         const float u = k2[(int64_t)i * 2], v = k2[(int64_t)i * 2 + 1];
         const float X = (float)((double)k3[j * 3] * sel.scale3d);
         const float Y = (float)((double)k3[j * 3 + 1] * sel.scale3d);
@@ -1620,8 +1605,6 @@ void pnp_ransac_kernel(
         o3[3 * q + 1] = Y;
         o3[3 * q + 2] = Z;
       }
-      base += sh.wave_cnt[0] + sh.wave_cnt[1] + sh.wave_cnt[2] + sh.wave_cnt[3];
-      __syncthreads();
     }
     n = base;
     if (t == 0) sel_counts[b] = n;
@@ -1657,13 +1640,7 @@ void pnp_ransac_kernel(
   }
   const float thr = (float)((double)reproj * (double)reproj);
   // @phase 1
-  if (t == 0) {
-    sh.iter = 0;
-    sh.niters = max(max_iters, 1);
-    sh.max_good = 0;
-    sh.done = (n == kModelPoints) ? 1 : 0;
-    sh.rng = 0xFFFFFFFFFFFFFFFFull;
-  }
+  if (t == 0) ransac_ctl_init(sh.ctl, max_iters, n == kModelPoints);
   __syncthreads();
   if (n == 4) {   // solvePnPRansac's 4-point branch: P3P gate, then EPnP over all four
     if (t == 0) sh.p3p = p3p_solutions(p2, p3, K4);
@@ -1683,51 +1660,22 @@ void pnp_ransac_kernel(
     return;
   }
 
-  while (!sh.done) {
+  while (!sh.ctl.done) {
     // getSubset x 64, in iteration order.  The round's draws are generated in parallel by
-    // jump-ahead (see mwc_mulmod; states at or above m -- the first draws from
-    // RNG((uint64)-1) -- are stepped by lane 0 first).  A subset takes draws until it has 5
-    // distinct indices, so the subset starting at draw s ends at a draw e(s) that depends on
-    // the draws alone: every thread evaluates e(s) for its positions, thread 0 chains
-    // s_{h+1} = e(s_h), and lane h deals subset h from s_h.  A chain that runs past the
-    // generated draws continues sequentially (rng_next) from that subset on.
-    if (wave == 0) {
-      if (lane == 0) {
-        unsigned long long z = sh.rng;
-        int k = 0;
-        while (z >= kMwcM && k < kRngPrefix) {
-          const unsigned v = rng_next(z);
-          sh.rst[k] = z;
-          sh.rii[k] = (int)(v % (unsigned)n);
-          ++k;
-        }
-        sh.rk = k;
-        sh.rz = z;
-      }
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-      __builtin_amdgcn_wave_barrier();
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-      const int k = sh.rk;
-      const unsigned long long z0 = sh.rz;
-      if (z0 < kMwcM) {
-        unsigned long long z = mwc_mulmod(z0, kMwcJumps.v[lane]);
-#pragma unroll
-        for (int i = 0; i < 6; ++i) {
-          const unsigned v = rng_next(z);
-          sh.rst[k + 6 * lane + i] = z;
-          sh.rii[k + 6 * lane + i] = (int)(v % (unsigned)n);
-        }
-      }
-      if (lane == 0) sh.rP = z0 < kMwcM ? k + 6 * 64 : k;
-    }
+    // jump-ahead (ransac_round_draws).  A subset takes draws until it has 5 distinct indices,
+    // so the subset starting at draw s ends at a draw e(s) that depends on the draws alone:
+    // every thread evaluates e(s) for its positions, thread 0 chains s_{h+1} = e(s_h), and
+    // lane h deals subset h from s_h.  A chain that runs past the generated draws continues
+    // sequentially (rng_next) from that subset on.
+    if (wave == 0) ransac_round_draws(sh.draws, sh.ctl, n);
     __syncthreads();
     {
-      const int P = sh.rP;
+      const int P = sh.draws.rP;
       // the 5 distinct draws from position s: their positions' end (one past the 5th) or -1
       auto deal = [&](int s0, int* out) __attribute__((always_inline)) {
         int c0 = -1, c1 = -1, c2 = -1, c3 = -1, got = 0, q = s0;
         while (got < kModelPoints && q < P) {
-          const int v = sh.rii[q++];
+          const int v = sh.draws.rii[q++];
           if (v == c0 || v == c1 || v == c2 || v == c3) continue;
           if (out) out[got] = v;
           if (got == 0) c0 = v;
@@ -1755,18 +1703,18 @@ void pnp_ransac_kernel(
       if (t == 0) {
         unsigned long long st;
         if (dealt == kRound) {   // the state after the last draw dealt
-          st = sh.rst[sh.rpos - 1];
+          st = sh.draws.rst[sh.rpos - 1];
         } else {   // sequential from subset `dealt`, at its start draw
           const int q0 = dealt > 0 ? sh.rend[sh.rstart[dealt - 1]] : 0;
-          st = q0 > 0 ? sh.rst[q0 - 1] : sh.rng;
+          st = q0 > 0 ? sh.draws.rst[q0 - 1] : sh.ctl.rng;
           int pos = q0;
           for (int h = dealt; h < kRound; ++h) {
             for (int i = 0; i < kModelPoints;) {
               int ii, j;
               for (;;) {
                 if (pos < P) {
-                  st = sh.rst[pos];
-                  ii = sh.rii[pos];
+                  st = sh.draws.rst[pos];
+                  ii = sh.draws.rii[pos];
                 } else {
                   ii = (int)(rng_next(st) % (unsigned)n);
                 }
@@ -1780,7 +1728,7 @@ void pnp_ransac_kernel(
             }
           }
         }
-        sh.rng = st;
+        sh.ctl.rng = st;
       }
     }
     __syncthreads();
@@ -1822,35 +1770,23 @@ void pnp_ransac_kernel(
     // lanes sweep the points)
     for (int hb = 0; hb < kRound; hb += 16) {
       for (int h = hb + wave; h < hb + 16; h += 4) {
-        int c = 0;
-        for (int i = lane; i < n; i += 64)
-          c += reproj_err2(sh.hypR[h], sh.hypT[h], K4, p3[3 * i], p3[3 * i + 1], p3[3 * i + 2],
-                           p2[2 * i], p2[2 * i + 1]) <= thr;
-#pragma unroll
-        for (int o = 32; o >= 1; o >>= 1) c += __shfl_xor(c, o, 64);
+        const int c = wave_count_if(lane, n, 64, [&](int i) {
+          return reproj_err2(sh.hypR[h], sh.hypT[h], K4, p3[3 * i], p3[3 * i + 1], p3[3 * i + 2],
+                             p2[2 * i], p2[2 * i + 1]) <= thr;
+        });
         if (lane == 0) sh.count[h] = c;
       }
       __syncthreads();
       if (t == 0) {  // in iteration order
-        int iter = sh.iter, niters = sh.niters, best = sh.max_good;
-        for (int h = hb; h < hb + 16 && iter < niters; ++h, ++iter) {
-          const int good = sh.count[h];
-          if (good > max(best, kModelPoints - 1)) {
-            best = good;
-            for (int i = 0; i < 3; ++i) {
-              sh.bestRvec[i] = sh.hypRvec[h][i];
-              sh.bestT[i] = sh.hypT[h][i];
-            }
-            niters = update_num_iters(confidence, (double)(n - good) / n, kModelPoints, niters);
+        ransac_accept(sh.ctl, sh.count, hb, hb + 16, n, confidence, kModelPoints, [&](int h) {
+          for (int i = 0; i < 3; ++i) {
+            sh.bestRvec[i] = sh.hypRvec[h][i];
+            sh.bestT[i] = sh.hypT[h][i];
           }
-        }
-        sh.iter = iter;
-        sh.niters = niters;
-        sh.max_good = best;
-        sh.done = iter >= niters;
+        });
       }
       __syncthreads();
-      if (sh.done) break;
+      if (sh.ctl.done) break;
     }
     // @phase 5
   }
@@ -1860,35 +1796,26 @@ void pnp_ransac_kernel(
     for (int i = t; i < n; i += kThreads) idx[i] = i;
     nin = n;
   } else {
-    if (sh.max_good <= 0) {
+    if (sh.ctl.max_good <= 0) {
       identity(2);
       return;
     }
     // inlier mask of the best model, compacted in point order
     double R[9];
     rodrigues_v2m(sh.bestRvec, R);
-    if (t == 0) sh.n_inl = 0;
-    __syncthreads();
-    for (int base = 0; base < n; base += kThreads) {
-      const int i = base + t;
+    nin = 0;
+    for (int start = 0; start < n; start += kThreads) {
+      const int i = start + t;
       bool in = false;
       if (i < n)
         in = reproj_err2(R, sh.bestT, K4, p3[3 * i], p3[3 * i + 1], p3[3 * i + 2], p2[2 * i],
                          p2[2 * i + 1]) <= thr;
-      const unsigned long long bal = __ballot(in);
-      if (lane == 0) sh.wave_cnt[wave] = __popcll(bal);
-      __syncthreads();
-      int off = sh.n_inl;
-      for (int w = 0; w < wave; ++w) off += sh.wave_cnt[w];
+      const int q = compact_step<4>(in, sh.wave_cnt, nin);
       if (in) {
-        idx[off + __popcll(bal & ((1ull << lane) - 1ull))] = i;
+        idx[q] = i;
         mask[i] = 1;
       }
-      __syncthreads();
-      if (t == 0) sh.n_inl += sh.wave_cnt[0] + sh.wave_cnt[1] + sh.wave_cnt[2] + sh.wave_cnt[3];
-      __syncthreads();
     }
-    nin = sh.n_inl;
   }
   // @phase 6
   if (n == kModelPoints)
@@ -1979,6 +1906,44 @@ size_t onepose_pnp_workspace_bytes(int batch, int max_points, int max_iters) {
   return align_up((size_t)batch * max_points * sizeof(int), 256);
 }
 
+// What onepose_pnp_ransac and onepose_pose_stage share once their own arguments are checked:
+// the remaining checks, then the RANSAC and the refit kernel.  The stage (sel.matches0 set)
+// compacts its points into out2 / out3 / out_counts, which the refit then reads; otherwise the
+// points are in2 / in3 / in_counts.  pose_gt null: no error outputs.
+static int launch_pose(const char* who, const float* in2, const float* in3, const int* in_counts,
+                       const SelArgs& sel, float* out2, float* out3, int* out_counts,
+                       int max_points, int batch, const double* K, int64_t K_bstride, double scale,
+                       float reproj_error, int max_iters, double confidence, double* pose34,
+                       uint8_t* inlier_mask, int* n_inliers, int* status, const double* pose_gt,
+                       int64_t gt_bstride, double* R_err_deg, double* t_err_cm, uint8_t* cmd,
+                       void* workspace, size_t workspace_bytes, hipStream_t st) {
+  OP_REQUIRE(confidence > 0 && confidence < 1, "%s: confidence %f not in (0,1)", who, confidence);
+  OP_REQUIRE(scale != 0.0, "%s: scale 0", who);
+  const size_t need = onepose_pnp_workspace_bytes(batch, max_points, max_iters);
+  if (!workspace || workspace_bytes < need) {
+    set_error("%s: workspace %zu < %zu bytes", who, workspace_bytes, need);
+    return ONEPOSE_ERR_WORKSPACE;
+  }
+  const size_t lds = kSharedBytes + (size_t)max_points * kPointBytes;
+  static bool attr_set = false;
+  if (!attr_set) {
+    OP_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(pnp_ransac_kernel),
+                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsBudget));
+    OP_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(pnp_refit_kernel),
+                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsBudget));
+    attr_set = true;
+  }
+  OP_LAUNCH(K_PNP, st, pnp_ransac_kernel, dim3(batch), dim3(kThreads), lds, st, in2, in3,
+            in_counts, max_points, K, K_bstride, scale, reproj_error, max_iters, confidence, pose34,
+            inlier_mask, n_inliers, status, static_cast<int*>(workspace), sel, out2, out3,
+            out_counts);
+  OP_LAUNCH(K_PNP_REFIT, st, pnp_refit_kernel, dim3(batch), dim3(kThreads), lds, st,
+            sel.matches0 ? out2 : in2, sel.matches0 ? out3 : in3, max_points, K, K_bstride, scale,
+            pose34, n_inliers, status, static_cast<const int*>(workspace), pose_gt, gt_bstride,
+            R_err_deg, t_err_cm, cmd);
+  return ONEPOSE_OK;
+}
+
 int onepose_pnp_ransac(const float* pts2d, const float* pts3d, const int* counts, int max_points,
                        const double* K, int64_t K_bstride, int batch, double scale,
                        float reproj_error, int max_iters, double confidence, double* pose34,
@@ -1991,32 +1956,10 @@ int onepose_pnp_ransac(const float* pts2d, const float* pts3d, const int* counts
   OP_REQUIRE(max_points <= onepose_pnp_max_points(),
              "pnp: max_points=%d above onepose_pnp_max_points() = %d (LDS)", max_points,
              onepose_pnp_max_points());
-  OP_REQUIRE(confidence > 0 && confidence < 1, "pnp: confidence %f not in (0,1)", confidence);
-  OP_REQUIRE(scale != 0.0, "pnp: scale 0");
-  const size_t need = onepose_pnp_workspace_bytes(batch, max_points, max_iters);
-  if (!workspace || workspace_bytes < need) {
-    set_error("pnp: workspace %zu < %zu bytes", workspace_bytes, need);
-    return ONEPOSE_ERR_WORKSPACE;
-  }
-  const size_t lds = kSharedBytes + (size_t)max_points * kPointBytes;
-  static bool attr_set = false;
-  if (!attr_set) {
-    OP_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(pnp_ransac_kernel),
-                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsBudget));
-    OP_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(pnp_refit_kernel),
-                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsBudget));
-    attr_set = true;
-  }
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  SelArgs none{};
-  OP_LAUNCH(K_PNP, st, pnp_ransac_kernel, dim3(batch), dim3(kThreads), lds, st, pts2d, pts3d,
-            counts, max_points, K, K_bstride, scale, reproj_error, max_iters, confidence, pose34,
-            inlier_mask, n_inliers, status, static_cast<int*>(workspace), none, nullptr, nullptr,
-            nullptr);
-  OP_LAUNCH(K_PNP_REFIT, st, pnp_refit_kernel, dim3(batch), dim3(kThreads), lds, st, pts2d, pts3d,
-            max_points, K, K_bstride, scale, pose34, n_inliers, status,
-            static_cast<const int*>(workspace), nullptr, (int64_t)0, nullptr, nullptr, nullptr);
-  return ONEPOSE_OK;
+  return launch_pose("pnp", pts2d, pts3d, counts, SelArgs{}, nullptr, nullptr, nullptr, max_points,
+                     batch, K, K_bstride, scale, reproj_error, max_iters, confidence, pose34,
+                     inlier_mask, n_inliers, status, nullptr, 0, nullptr, nullptr, nullptr,
+                     workspace, workspace_bytes, static_cast<hipStream_t>(stream));
 }
 
 int onepose_pose_stage(const int64_t* matches0, const float* kpts2d, int64_t kpts2d_bstride,
@@ -2036,34 +1979,11 @@ int onepose_pose_stage(const int64_t* matches0, const float* kpts2d, int64_t kpt
   OP_REQUIRE(n1 <= onepose_pnp_max_points(),
              "pose_stage: n1=%d above onepose_pnp_max_points() = %d (LDS)", n1,
              onepose_pnp_max_points());
-  OP_REQUIRE(confidence > 0 && confidence < 1, "pose_stage: confidence %f not in (0,1)",
-             confidence);
-  OP_REQUIRE(scale != 0.0, "pose_stage: scale 0");
-  const int max_points = n1;
-  const size_t need = onepose_pnp_workspace_bytes(batch, max_points, max_iters);
-  if (!workspace || workspace_bytes < need) {
-    set_error("pose_stage: workspace %zu < %zu bytes", workspace_bytes, need);
-    return ONEPOSE_ERR_WORKSPACE;
-  }
-  const size_t lds = kSharedBytes + (size_t)max_points * kPointBytes;
-  static bool attr_set = false;
-  if (!attr_set) {
-    OP_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(pnp_ransac_kernel),
-                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsBudget));
-    OP_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(pnp_refit_kernel),
-                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsBudget));
-    attr_set = true;
-  }
-  hipStream_t st = static_cast<hipStream_t>(stream);
   const SelArgs sel{matches0, kpts2d, kpts2d_bstride, kpts3d, kpts3d_bstride, n1, n3, scale};
-  OP_LAUNCH(K_PNP, st, pnp_ransac_kernel, dim3(batch), dim3(kThreads), lds, st, nullptr, nullptr,
-            nullptr, max_points, K, K_bstride, scale, reproj_error, max_iters, confidence, pose34,
-            inlier_mask, n_inliers, status, static_cast<int*>(workspace), sel, pts2d, pts3d,
-            counts);
-  OP_LAUNCH(K_PNP_REFIT, st, pnp_refit_kernel, dim3(batch), dim3(kThreads), lds, st, pts2d, pts3d,
-            max_points, K, K_bstride, scale, pose34, n_inliers, status,
-            static_cast<const int*>(workspace), pose_gt, gt_bstride, R_err_deg, t_err_cm, cmd);
-  return ONEPOSE_OK;
+  return launch_pose("pose_stage", nullptr, nullptr, nullptr, sel, pts2d, pts3d, counts, n1, batch,
+                     K, K_bstride, scale, reproj_error, max_iters, confidence, pose34, inlier_mask,
+                     n_inliers, status, pose_gt, gt_bstride, R_err_deg, t_err_cm, cmd, workspace,
+                     workspace_bytes, static_cast<hipStream_t>(stream));
 }
 
 }  // extern "C"

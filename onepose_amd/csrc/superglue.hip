@@ -481,16 +481,6 @@ __device__ __forceinline__ void lse_merge(double& m1, double& s1, double m2, dou
   s1 = s1 * exp(m1 - M) + s2 * exp(m2 - M);
   m1 = M;
 }
-__device__ __forceinline__ double wave_max_d(double v) {
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) v = fmax(v, __shfl_xor(v, o, 64));
-  return v;
-}
-__device__ __forceinline__ double wave_sum_d(double v) {
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
 __device__ __forceinline__ double sk_alpha(const SkArgs& A) {
   return (double)(A.alpha_p != nullptr ? *A.alpha_p : A.alpha_v);
 }

@@ -26,6 +26,9 @@ CASES = {
                    n0=700, n1=600, pad=7, seed=11),
     "per_view": dict(spec=((40, 30), (64, 20), (33, 33)), n0=70, n1=90, pad=1, seed=12,
                      per_view=True),
+    # the in-kernel scan over two 256-thread trips: every view has an estimate, and the valid
+    # matches of views 0 and 1 cross the wave boundaries and the trip boundary
+    "two_trips": dict(spec=((280, 200), (257, 180), (64, 40)), n0=300, n1=320),
 }
 
 
@@ -75,6 +78,8 @@ def test_stage_equals_the_oracle(cases, device, name):
         assert r0[1] == r0[6] == r0.max() and r1[1] == r1[6] == r1.max()
         assert refs[0]["best_view"] == refs[1]["best_view"] == 1
         assert list(refs[0]["bbox"][2]) == [0, 0, 480, 640]   # x1 is the query's height
+    if name == "two_trips":
+        assert list(refs[0]["counts"]) == [280, 257, 64] and not refs[0]["status"].any()
 
 
 def test_stage_equals_its_parts(cases, device):
