@@ -637,6 +637,61 @@ int onepose_crop_resize(const uint8_t* image, int h, int w, const int* bbox, con
                         int* crop_status, void* stream);
 
 /* ------------------------------------------------------------------------------------ *
+ * NearestNeighbour 2D-2D matcher  --  replaces NearestNeighbour.forward
+ *   (src/models/matchers/nn/nearest_neighbour.py: the einsum :42, find_nn :5-15 for rows and
+ *    for columns :43-49, mutual_check :18-23), the matcher the reference's tracker runs per frame.
+ * This family is versioned on its own, as the SuperGlue and detector families:
+ * onepose_nn_version() returns 1; onepose_abi_version() was not bumped for it.
+ *
+ * sim[b][i][j] = sum_k desc0[b][k][i] desc1[b][k][j] is never stored: launch 1 is an fp32 MFMA
+ * tile GEMM whose epilogue keeps, per 64 x 64 block, each row's and each column's (best value,
+ * best index, second value); launch 2 merges those partials and applies find_nn's tests;
+ * launch 3 (do_mutual_check only) is mutual_check.  Deterministic, no atomics.
+ *
+ * Kept from the reference:
+ *  - a threshold that is not > 0 (the reference's falsy None / 0) or is NaN disables its test;
+ *  - fp32 test arithmetic in the reference's order: dist = 2 * (1 - sim) is one subtraction and
+ *    an exact doubling; ratio: dist_best <= float32(ratio ** 2) * dist_second, one multiply;
+ *    distance: dist_best <= float32(distance ** 2); score (sim_best + 1) / 2, or 0 and -1;
+ *  - only matches0 gets the mutual check: matches1 is the raw column result, mscores0 is NOT
+ *    zeroed where the check clears matches0, and without the check matches0 is the raw row result;
+ *  - descriptors are not normalised here: sim may leave [-1, 1] and dist may be negative;
+ *  - the ratio test needs two candidates on both searched sides (topk(2) raises in the
+ *    reference): n0 == 1 or n1 == 1 with a ratio test is ONEPOSE_ERR_INVALID;
+ *  - the reference's conf key match_threshold is never read there and has no argument here.
+ * Decided here (torch.topk promises no order on equal values): the best is the LOWEST index
+ * among equal similarities, and the second value is the second element of the multiset, so a
+ * duplicated best value is its own runner-up.  sim[i][j] is summed over k in one fixed order
+ * wherever (i, j) lies in a tile, so bit-equal descriptor columns give bit-equal similarities.
+ * NaN or infinite descriptors are outside the contract (a row that compares above nothing is
+ * unmatched).
+ *
+ * desc0 [batch, d, n0], desc1 [batch, d, n1] in the reference's layout, fp32 (ONEPOSE_DT_F32)
+ * or fp16 (ONEPOSE_DT_F16, converted as loaded: results are those of the fp32 call on the
+ * upcast values, bit for bit); batch strides in elements, 0 = that side is shared by the batch.
+ * 1 <= n0, n1 <= 16384, 1 <= d <= 1024 (any value), 1 <= batch <= 65535.
+ * Outputs matches0 [batch, n0], matches1 [batch, n1] int64 (-1 = none), mscores0/1 fp32.
+ * Checks, in this order, before anything is launched: null pointers (descriptors, outputs,
+ * workspace); batch; n0 and n1; d; desc_dtype; negative strides; the ratio test's two
+ * candidates -- all ONEPOSE_ERR_INVALID -- then the workspace size (ONEPOSE_ERR_WORKSPACE).
+ * onepose_nn_match_workspace_bytes returns 0 for a refused shape.  The entry points never
+ * allocate, free or synchronise and can be captured in a graph.  All device pointers.
+ * onepose_nn_similarity_top2 is launch 1 alone (the partials stay in the workspace), for
+ * measurement: the profile hook's kinds below are a closed list, so the launches of this
+ * family are not bracketed by it.
+ * ------------------------------------------------------------------------------------ */
+int onepose_nn_version(void);
+size_t onepose_nn_match_workspace_bytes(int batch, int n0, int n1);
+int onepose_nn_match(const void* desc0, int64_t desc0_bstride, const void* desc1,
+                     int64_t desc1_bstride, int desc_dtype, int batch, int d, int n0, int n1,
+                     double ratio_threshold, double distance_threshold, int do_mutual_check,
+                     int64_t* matches0, int64_t* matches1, float* mscores0, float* mscores1,
+                     void* workspace, size_t workspace_bytes, void* stream);
+int onepose_nn_similarity_top2(const void* desc0, int64_t desc0_bstride, const void* desc1,
+                               int64_t desc1_bstride, int desc_dtype, int batch, int d, int n0,
+                               int n1, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------ *
  * Measurement hook (bench.py's roofline). While enabled, every launch whose kernel kind
  * is in `kind_mask` (bit k = kind k, names from onepose_profile_kind_name) is bracketed by
  * two HIP events recorded on the launch's own stream.  Host-side state, not for use during

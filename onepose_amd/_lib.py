@@ -166,6 +166,15 @@ PROTOTYPES = {
                                      c_void_p, c_size_t, c_void_p]),
     "onepose_crop_resize": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_int,
                                     c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "onepose_nn_version": (c_int, []),
+    "onepose_nn_match_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "onepose_nn_match": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int,
+                                 c_int, c_int, c_int, c_int, c_double, c_double, c_int,
+                                 c_void_p, c_void_p, c_void_p, c_void_p,
+                                 c_void_p, c_size_t, c_void_p]),
+    "onepose_nn_similarity_top2": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int,
+                                           c_int, c_int, c_int, c_int,
+                                           c_void_p, c_size_t, c_void_p]),
     "onepose_profile_begin": (c_int, [ctypes.c_uint64, c_int]),
     "onepose_profile_begin_device": (c_int, [ctypes.c_uint64]),
     "onepose_profile_end_device": (c_int, [c_void_p, c_void_p, c_int]),

@@ -405,3 +405,34 @@ def make_superglue_inputs(n0: int, n1: int, seed: int = 0, batch: int = 1,
         "image0": np.zeros((batch, 1, SUPERGLUE_IMAGE, SUPERGLUE_IMAGE), f32),
         "image1": np.zeros((b1, 1, SUPERGLUE_IMAGE, SUPERGLUE_IMAGE), f32),
     }
+
+
+def make_nn_inputs(n0: int, n1: int, seed: int, batch: int = 1, shared1: bool = False,
+                   d: int = DESC_DIM, inlier_frac: float = 0.6,
+                   noise: float = 0.3) -> dict[str, np.ndarray]:
+    """``descriptors0 [B,d,n0]`` / ``descriptors1 [B or 1,d,n1]`` for ``NearestNeighbour.forward``
+    (nearest_neighbour.py:41-42) as unit-norm float32 columns.  ``int(inlier_frac * min(n0, n1))``
+    columns of each side, at random positions, are noisy copies of common unit sources (a
+    perturbation of norm about ``noise``, then renormalised); the rest are random directions.
+    With ``shared1`` side 1 is one set for the whole batch, returned with batch dimension 1."""
+    rs = np.random.RandomState(seed)
+    n_src = int(inlier_frac * min(n0, n1))
+
+    def side(n, src):
+        x = _unit_rows(rs.standard_normal((n, d)))
+        pos = rs.permutation(n)[:n_src]
+        x[pos] = _unit_rows(src + noise / np.sqrt(d) * rs.standard_normal((n_src, d)))
+        return x
+
+    d0, d1 = [], []
+    src = None
+    for b in range(batch):
+        if not (shared1 and b > 0):
+            src = _unit_rows(rs.standard_normal((n_src, d)))
+            d1.append(side(n1, src))
+        d0.append(side(n0, src))
+    f32 = np.float32
+    return {
+        "descriptors0": np.ascontiguousarray(np.stack(d0).transpose(0, 2, 1)).astype(f32),
+        "descriptors1": np.ascontiguousarray(np.stack(d1).transpose(0, 2, 1)).astype(f32),
+    }
