@@ -692,6 +692,98 @@ int onepose_nn_similarity_top2(const void* desc0, int64_t desc0_bstride, const v
                                int n1, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------ *
+ * Tracker back end  --  bundle adjustment and triangulation, fp64
+ *   onepose_ba_solve replaces BATracker.apply_ba's call of DeepLM's Solve
+ *   (src/tracker/ba_tracker.py:358-441, the call at :401-407) with the cost function
+ *   SnavelyReprojectionErrorV2 / AngleAxisRotatePoint (src/tracker/tracking_utils.py:91-169);
+ *   onepose_triangulate replaces apply_triangulation (:267-273, cv2.triangulatePoints) together
+ *   with track_ba's reprojection and depth filters (:556-571).
+ * Versioned on its own: onepose_ba_version() returns 1; onepose_abi_version() was not bumped.
+ *
+ * What the reference pins: the cost function only.  residual[n] = f (R(aa) X + t).xy / (.).z +
+ * (cx, cy) - (u, v) with X = points[ptIdx[n]], (aa, t) = cam_pose[camIdx[n]], (u, v, f, cx, cy) =
+ * features[n]; the rotation takes the reference's two branches (theta^2 > 0: Rodrigues, else
+ * X + aa x X), and at theta^2 == 0 the Jacobian is that branch's derivative, -[X]x.  DeepLM's
+ * source is not in the reference tree and cv2 is not a dependency here, so the solver below is
+ * this project's own (parity with DeepLM's iterates and with cv2's SVD is NOT verified); it is
+ * restated in numpy float64 in tests/ba_oracle.py, which the GPU tests compare against.
+ *
+ * The solver: Ceres-style Levenberg-Marquardt, cost = 1/2 sum |residual|^2.  Per iteration:
+ *   U_c = sum Jc^T Jc, V_p = sum Jp^T Jp, W_n = Jc^T Jp, g = J^T r at the current iterate;
+ *   damping mu * clamp(diag, 1e-6, 1e32) with mu = 1 / radius is added to diag U and diag V;
+ *   S = U - sum_p W V_p^-1 W^T over the active cameras, Cholesky, S dc = -g_c + W V^-1 g_p,
+ *   dp = V^-1 (-g_p - W^T dc), where V_p^-1 is applied through its Cholesky factor (V = L L^T,
+ *   Y = L^-1 W^T, W V^-1 W^T = Y^T Y) and never formed: an explicit inverse of a point seen by
+ *   few cameras would cost S its accuracy;  candidate cost', model decrease md = -(J d).(r + J d / 2),
+ *   rho = (cost - cost') / md;  accepted iff cost' is finite, md > 0 and rho > 1e-3.
+ *   Accepted: radius = min(radius / max(1/3, 1 - (2 rho - 1)^3), 1e16), decrease factor = 2.
+ *   Rejected, or a Cholesky pivot that is not > 0: radius /= factor, factor *= 2.
+ * It stops after max_iters iterations or max_success accepted ones (the reference passes 5 and
+ * 5; there are no convergence tolerances).  Only cameras and points with at least one
+ * observation (the active ones) move; the others are never written.  On return the variables are
+ * the last accepted iterate.  A non-finite initial cost gives status 1 with nothing moved.
+ *
+ * info [104] fp64, device: [0] status (0 ran, 1 non-finite initial cost, 2 the index does not
+ * describe ptIdx / camIdx), [1] iterations, [2] accepted iterations, [3] initial cost, [4] final
+ * cost, [5] final radius, [6..7] 0; then one row of 6 per iteration from [8]: cost, candidate
+ * cost, model decrease, rho, the radius used, accepted (a failed Cholesky: NaN, NaN, NaN).
+ *
+ * The index (host): onepose_ba_build_index sorts the observations by camera and by point
+ * (stable: ties stay in observation order) and lists the active cameras and points, into
+ * onepose_ba_index_bytes(n_obs, n_cams, n_points) bytes of int32 words; it needs no GPU.  An id
+ * outside [0, n_cams) / [0, n_points) is ONEPOSE_ERR_INVALID.  The caller uploads those bytes and
+ * passes the two counts to the solve, whose first kernels check on the device that every id is in
+ * range and that every CSR range holds, in observation order, exactly the observations of the
+ * key it claims; on any mismatch the solve reports status 2 and moves nothing (nothing is
+ * dereferenced through an unchecked index).
+ *
+ * points [n_points, 3], cam_pose [n_cams, 6], features [n_obs, 5] fp64; ptIdx, camIdx [n_obs]
+ * int64.  1 <= n_obs <= 2^20, 1 <= n_cams, n_points <= 2^20, active cameras <=
+ * onepose_ba_max_active_cameras() (24: the reference's windows are 10 and 20 keyframes plus the
+ * current frame).  Checks of onepose_ba_solve, in this order, before anything is launched: null
+ * pointers; shapes (sizes, active counts within 1..n); active cameras over the limit; max_iters
+ * outside 1..16; max_success < 1; initial_radius not positive and finite -- all
+ * ONEPOSE_ERR_INVALID -- then the workspace size (ONEPOSE_ERR_WORKSPACE).
+ * onepose_ba_workspace_bytes returns 0 for a refused shape.
+ *
+ * onepose_ba_linearize is the first stage alone on the caller's arrays (no index): residuals
+ * [n_obs, 2], Jc [n_obs, 2, 6], Jp [n_obs, 2, 3], cost [1].  An observation whose ids are out of
+ * range gets NaN rows (and the cost is NaN); nothing is read through them.
+ *
+ * onepose_triangulate: P1, P2 [3, 4] projection matrices (K inv(Tcw)[:3]), pts1, pts2 [n, 2]
+ * pixels -> X [n, 3], err1, err2 [n] (reprojection error in each view), z [n] (= X[:, 2]), keep
+ * [n] uint8 = err1 <= rep_thr && err2 <= rep_thr && z <= z_max (the reference removes > 20 and
+ * > 0.15); a pair with w == 0 or any non-finite result is not kept.  One thread per pair: the
+ * 4 x 4 DLT matrix A, the eigenvector of A^T A's smallest eigenvalue by cyclic Jacobi (the
+ * reference's own _triangulatePy, :243-265, also works on A^T A), dehomogenised.
+ *
+ * No entry point allocates, frees or synchronises; all can be captured in a graph.  No
+ * floating-point atomics and a fixed order in every sum: results are bit-identical from run to
+ * run and on any stream.  All pointers are device pointers except those of
+ * onepose_ba_build_index, which are host pointers.  The profile hook's kinds are a closed list,
+ * so the launches of this family are not bracketed by it.
+ * ------------------------------------------------------------------------------------ */
+int onepose_ba_version(void);
+int onepose_ba_max_active_cameras(void);
+size_t onepose_ba_index_bytes(int64_t n_obs, int n_cams, int n_points);
+int onepose_ba_build_index(const int64_t* ptIdx, const int64_t* camIdx, int64_t n_obs, int n_cams,
+                           int n_points, void* index, size_t index_bytes, int* n_active_cams,
+                           int* n_active_points);
+size_t onepose_ba_workspace_bytes(int64_t n_obs, int n_active_cams, int n_active_points);
+int onepose_ba_solve(double* points, double* cam_pose, const double* features,
+                     const int64_t* ptIdx, const int64_t* camIdx, const void* index,
+                     int64_t n_obs, int n_cams, int n_points, int n_active_cams,
+                     int n_active_points, int max_iters, int max_success, double initial_radius,
+                     double* info, void* workspace, size_t workspace_bytes, void* stream);
+int onepose_ba_linearize(const double* points, const double* cam_pose, const double* features,
+                         const int64_t* ptIdx, const int64_t* camIdx, int64_t n_obs, int n_cams,
+                         int n_points, double* residuals, double* Jc, double* Jp, double* cost,
+                         void* stream);
+int onepose_triangulate(const double* P1, const double* P2, const double* pts1,
+                        const double* pts2, int n, double rep_thr, double z_max, double* X,
+                        double* err1, double* err2, double* z, uint8_t* keep, void* stream);
+
+/* ------------------------------------------------------------------------------------ *
  * Measurement hook (bench.py's roofline). While enabled, every launch whose kernel kind
  * is in `kind_mask` (bit k = kind k, names from onepose_profile_kind_name) is bracketed by
  * two HIP events recorded on the launch's own stream.  Host-side state, not for use during

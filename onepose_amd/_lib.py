@@ -175,6 +175,21 @@ PROTOTYPES = {
     "onepose_nn_similarity_top2": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int,
                                            c_int, c_int, c_int, c_int,
                                            c_void_p, c_size_t, c_void_p]),
+    "onepose_ba_version": (c_int, []),
+    "onepose_ba_max_active_cameras": (c_int, []),
+    "onepose_ba_index_bytes": (c_size_t, [c_int64, c_int, c_int]),
+    "onepose_ba_build_index": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_int, c_void_p,
+                                       c_size_t, ctypes.POINTER(c_int), ctypes.POINTER(c_int)]),
+    "onepose_ba_workspace_bytes": (c_size_t, [c_int64, c_int, c_int]),
+    "onepose_ba_solve": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                 c_int64, c_int, c_int, c_int, c_int, c_int, c_int, c_double,
+                                 c_void_p, c_void_p, c_size_t, c_void_p]),
+    "onepose_ba_linearize": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                     c_int64, c_int, c_int, c_void_p, c_void_p, c_void_p,
+                                     c_void_p, c_void_p]),
+    "onepose_triangulate": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_double,
+                                    c_double, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                    c_void_p]),
     "onepose_profile_begin": (c_int, [ctypes.c_uint64, c_int]),
     "onepose_profile_begin_device": (c_int, [ctypes.c_uint64]),
     "onepose_profile_end_device": (c_int, [c_void_p, c_void_p, c_int]),

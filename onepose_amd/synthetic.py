@@ -436,3 +436,119 @@ def make_nn_inputs(n0: int, n1: int, seed: int, batch: int = 1, shared1: bool = 
         "descriptors0": np.ascontiguousarray(np.stack(d0).transpose(0, 2, 1)).astype(f32),
         "descriptors1": np.ascontiguousarray(np.stack(d1).transpose(0, 2, 1)).astype(f32),
     }
+
+
+def _rodrigues_np(aa):
+    th = np.linalg.norm(aa)
+    K = np.array([[0.0, -aa[2], aa[1]], [aa[2], 0.0, -aa[0]], [-aa[1], aa[0], 0.0]])
+    if th == 0.0:
+        return np.eye(3)
+    return np.eye(3) + np.sin(th) / th * K + (1.0 - np.cos(th)) / th ** 2 * (K @ K)
+
+
+def make_ba_problem(seed: int, n_cams: int, n_points: int, n_obs: int, active_cams: int = None,
+                    observed_points: int = None, dist=(0.35, 0.5), perturb: float = 1.0,
+                    zero_rot_cam: bool = False, once_point: bool = False,
+                    duplicate: bool = False, noise_px: float = 0.5) -> dict[str, np.ndarray]:
+    """A bundle adjustment problem as ``BATracker.apply_ba`` hands it to ``Solve``
+    (ba_tracker.py:358-407): ``points [P,3]``, ``cam_pose [C,6]`` (angle-axis, t), ``features
+    [N,5]`` = (u, v, f, cx, cy), ``ptIdx`` / ``camIdx [N]`` int64, all float64 otherwise.
+
+    The object fills +-5 cm; cameras stand ``dist`` metres away with f in 450..650 and look at it
+    under random rotations.  ``active_cams`` of the cameras and ``observed_points`` of the points
+    (random subsets, default all) carry the ``n_obs`` observations: each of them at least one,
+    (camera, point) pairs distinct.  Pixels are the true projections plus ``noise_px`` of normal
+    noise; the returned variables are the true ones perturbed by ``perturb`` x (3 mm, 0.01 rad,
+    3 mm).  ``zero_rot_cam``: the first active camera has angle-axis exactly 0, before and after
+    the perturbation.  ``once_point``: one observed point is seen exactly once.  ``duplicate``:
+    the last observation repeats the first one's (camera, point) pair with its own pixel noise."""
+    rs = np.random.RandomState(seed)
+    C, P, N = n_cams, n_points, n_obs
+    A = C if active_cams is None else active_cams
+    Q = P if observed_points is None else observed_points
+    pts = rs.uniform(-0.05, 0.05, (P, 3))
+    axis = rs.standard_normal((C, 3))
+    axis /= np.linalg.norm(axis, axis=1, keepdims=True)
+    aa = axis * rs.uniform(0.2, 2.5, (C, 1))
+    t = np.concatenate([rs.uniform(-0.02, 0.02, (C, 2)), rs.uniform(dist[0], dist[1], (C, 1))], 1)
+    intr = np.concatenate([rs.uniform(450.0, 650.0, (C, 1)), rs.uniform(246.0, 266.0, (C, 2))], 1)
+    cams_on = np.sort(rs.permutation(C)[:A])
+    pts_on = np.sort(rs.permutation(P)[:Q])
+    if zero_rot_cam:
+        aa[cams_on[0]] = 0.0
+    n_free = N - int(duplicate) - int(once_point)
+    pool = pts_on[:-1] if once_point else pts_on
+    assert n_free >= max(A, len(pool)) and n_free <= A * len(pool), "n_obs does not fit"
+    pairs = set()
+    order = []
+    for k in range(max(A, len(pool))):          # everyone at least once
+        pr = (int(cams_on[k % A]), int(pool[k % len(pool)]))
+        if pr not in pairs:
+            pairs.add(pr)
+            order.append(pr)
+    while len(order) < n_free:
+        pr = (int(cams_on[rs.randint(A)]), int(pool[rs.randint(len(pool))]))
+        if pr not in pairs:
+            pairs.add(pr)
+            order.append(pr)
+    order = [order[i] for i in rs.permutation(len(order))]
+    if once_point:
+        order.insert(len(order) // 2, (int(cams_on[-1]), int(pts_on[-1])))
+    if duplicate:
+        order.append(order[0])
+    cam_idx = np.array([c for c, _ in order], dtype=np.int64)
+    pt_idx = np.array([p for _, p in order], dtype=np.int64)
+    feats = np.zeros((N, 5))
+    for n in range(N):
+        c, p = cam_idx[n], pt_idx[n]
+        x = _rodrigues_np(aa[c]) @ pts[p] + t[c]
+        feats[n, :2] = intr[c, 0] * x[:2] / x[2] + intr[c, 1:] + noise_px * rs.standard_normal(2)
+        feats[n, 2:] = intr[c]
+    d_aa = perturb * 0.01 * rs.standard_normal((C, 3))
+    if zero_rot_cam:
+        d_aa[cams_on[0]] = 0.0
+    cam_pose = np.concatenate([aa + d_aa, t + perturb * 0.003 * rs.standard_normal((C, 3))], 1)
+    return {
+        "points": pts + perturb * 0.003 * rs.standard_normal((P, 3)),
+        "cam_pose": cam_pose,
+        "features": feats,
+        "ptIdx": pt_idx,
+        "camIdx": cam_idx,
+    }
+
+
+def make_triangulation_inputs(n: int, seed: int) -> dict[str, np.ndarray]:
+    """Two views of ``n`` points for ``BATracker.apply_triangulation`` (ba_tracker.py:267-273):
+    ``K1, K2 [3,3]``, ``Tcw1, Tcw2 [4,4]`` (the inverses of the object-to-camera poses, as
+    track_ba passes them, :549-554), ``kpt2d_1, kpt2d_2 [n,2]``, float64.  The views are 0.4 m
+    from a +-5 cm object and at least 5 degrees apart.  About a tenth of the pairs each are
+    pushed past one of track_ba's filters (:556-571): a pixel displaced by 40..80 px in view 1,
+    one in view 2, and a point with world z in 0.2..0.3; the rest carry 0.5 px of noise."""
+    rs = np.random.RandomState(seed)
+    Ks, poses = [], []
+    axis = rs.standard_normal(3)
+    axis /= np.linalg.norm(axis)
+    base = rs.uniform(0.3, 1.5)
+    for v in range(2):
+        ang = base + v * np.deg2rad(rs.uniform(8.0, 25.0))
+        T = np.eye(4)
+        T[:3, :3] = _rodrigues_np(axis * ang)
+        T[:3, 3] = [rs.uniform(-0.02, 0.02), rs.uniform(-0.02, 0.02), rs.uniform(0.38, 0.42)]
+        poses.append(T)
+        f = rs.uniform(450.0, 650.0)
+        Ks.append(np.array([[f, 0.0, rs.uniform(246, 266)], [0.0, f, rs.uniform(246, 266)],
+                            [0.0, 0.0, 1.0]]))
+    X = rs.uniform(-0.05, 0.05, (n, 3))
+    kind = rs.randint(0, 10, n) if n > 1 else np.full(1, 9)
+    X[kind == 2, 2] = rs.uniform(0.2, 0.3, int((kind == 2).sum()))
+    uv = []
+    for v in range(2):
+        x = X @ poses[v][:3, :3].T + poses[v][:3, 3]
+        p = x @ Ks[v].T
+        p = p[:, :2] / p[:, 2:] + 0.5 * rs.standard_normal((n, 2))
+        far = kind == v
+        ang = rs.uniform(0.0, 2.0 * np.pi, n)
+        p[far] += (rs.uniform(40.0, 80.0, n)[:, None] * np.stack([np.cos(ang), np.sin(ang)], 1))[far]
+        uv.append(p)
+    return {"K1": Ks[0], "K2": Ks[1], "Tcw1": np.linalg.inv(poses[0]),
+            "Tcw2": np.linalg.inv(poses[1]), "kpt2d_1": uv[0], "kpt2d_2": uv[1]}

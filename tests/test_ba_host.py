@@ -1,0 +1,320 @@
+"""Tracker back end, host side (no GPU): the numpy oracle's cost function against the fixtures
+recorded from the reference, the oracle's solver against its own recorded results, the host-only
+index builder through ctypes, every entry point's refusals (all before any launch) and their
+order, and the window rule of apply_ba's host half."""
+import ctypes
+import os
+
+import numpy as np
+import pytest
+import torch
+
+import ba_cases
+import ba_oracle as O
+from onepose_amd import _lib, synthetic, tracker
+
+OK, INVALID, WORKSPACE = 0, 1, 4
+
+
+@pytest.fixture(scope="module")
+def lib():
+    return _lib.load()
+
+
+@pytest.fixture(scope="module")
+def lin():
+    return np.load(os.path.join(ba_cases.GOLDEN, "ba_lin.npz"))
+
+
+@pytest.fixture(scope="module")
+def solved():
+    return np.load(os.path.join(ba_cases.GOLDEN, "ba_solve.npz"))
+
+
+@pytest.mark.parametrize("name", sorted(ba_cases.LIN_CASES))
+def test_oracle_cost_function_matches_the_reference(name, lin):
+    """|d residual| <= 1e-9 px and |d J| <= 1e-9 max|J|: fp64 eps x magnitudes <= 2e3 x a chain of
+    fewer than 100 operations is 4e-11, with a 10 x margin and rounded up."""
+    prob = ba_cases.problem(name, int(lin[f"{name}_seed"]))
+    assert ba_cases.problem_sha(prob) == str(lin[f"{name}_sha"]), "synthetic inputs changed"
+    r, Jc, Jp = O.linearize(prob["points"], prob["cam_pose"], prob["features"], prob["ptIdx"],
+                            prob["camIdx"])
+    assert np.abs(r - lin[f"{name}_r"]).max() <= 1e-9
+    for got, ref in ((Jc, lin[f"{name}_Jc"]), (Jp, lin[f"{name}_Jp"])):
+        assert got.shape == ref.shape
+        assert np.abs(got - ref).max() <= 1e-9 * np.abs(ref).max()
+    if name == "lin_zero_rot":   # the theta^2 == 0 branch is in the fixture
+        assert (np.abs(prob["cam_pose"][prob["camIdx"], :3]).sum(1) == 0).any()
+
+
+@pytest.mark.parametrize("name", ["one", "tiny", "n257", "reject"])
+def test_oracle_reproduces_its_fixture(name, solved):
+    prob, radius, exp = ba_cases.load_solve(name, solved)
+    pts, cams, info = O.solve(prob["points"], prob["cam_pose"], prob["features"], prob["ptIdx"],
+                              prob["camIdx"], 5, 5, radius)
+    assert np.array_equal(pts, exp["points"]) and np.array_equal(cams, exp["cam_pose"])
+    assert np.array_equal(info, exp["info"], equal_nan=True)
+    assert info[4] < info[3] and info[0] == O.ST_OK
+
+
+def test_fixture_trajectories(solved):
+    """The recorded tolerances are positive, and the case `reject` holds a rejected step with a
+    model decrease above 1e-6 x cost and rho at least 0.05 from the acceptance threshold."""
+    for name in ba_cases.SOLVE_CASES:
+        info, tol = solved[f"{name}_info"], solved[f"{name}_tol"]
+        assert tol.shape == (5,) and (tol >= 1e-12).all() and tol[0] <= 16e-6
+        rw, sig = O.rows(info), O.significant(info)
+        assert len(rw) == 5 or info[2] == 5
+        assert (np.abs(rw[sig, 3] - O.MIN_RHO) >= 0.05).all()
+    rw, sig = O.rows(solved["reject_info"]), O.significant(solved["reject_info"])
+    assert ((rw[:, 5] == 0) & sig).any() and ((rw[:, 5] == 1) & sig).any()
+
+
+def test_oracle_leaves_unobserved_variables_alone():
+    prob = synthetic.make_ba_problem(3, 8, 30, 60, active_cams=4, observed_points=20)
+    pts, cams, info = O.solve(prob["points"], prob["cam_pose"], prob["features"], prob["ptIdx"],
+                              prob["camIdx"])
+    idle_c = np.setdiff1d(np.arange(8), prob["camIdx"])
+    idle_p = np.setdiff1d(np.arange(30), prob["ptIdx"])
+    assert len(idle_c) == 4 and len(idle_p) == 10
+    assert np.array_equal(cams[idle_c], prob["cam_pose"][idle_c])
+    assert np.array_equal(pts[idle_p], prob["points"][idle_p])
+    assert not np.array_equal(cams, prob["cam_pose"])
+    bad = prob["features"].copy()
+    bad[5, 0] = np.nan
+    p2, c2, i2 = O.solve(prob["points"], prob["cam_pose"], bad, prob["ptIdx"], prob["camIdx"])
+    assert i2[0] == O.ST_FAILED and np.array_equal(p2, prob["points"])
+
+
+def test_versions(lib):
+    assert lib.onepose_ba_version() == 1 == tracker.BA_VERSION
+    assert lib.onepose_abi_version() == 9
+    assert lib.onepose_ba_max_active_cameras() >= 24
+    assert tracker.INFO_DOUBLES == O.INFO_DOUBLES == 104
+
+
+# ---- the index builder ------------------------------------------------------------------------
+def _check_index(prob, C, P):
+    buf, A, Pa = tracker.build_index(prob["ptIdx"], prob["camIdx"], C, P)
+    N = len(prob["ptIdx"])
+    ix = ba_cases.parse_index(buf, N, C, P)
+    ref = O.build_index(prob["ptIdx"], prob["camIdx"], C, P)
+    assert list(ix["head"][:6]) == [ix["head"][0], N, C, P, A, Pa]
+    assert A == len(ref["act_cams"]) and Pa == len(ref["act_pts"])
+    for k in ("act_cams", "act_pts", "cam_start", "pt_start", "cam_order", "pt_order"):
+        assert np.array_equal(ix[k], ref[k]), k
+    return ix, A, Pa
+
+
+def test_build_index_orders_are_stable():
+    prob = synthetic.make_ba_problem(1, 5, 80, 257, duplicate=True)
+    ix, A, Pa = _check_index(prob, 5, 80)
+    assert A == 5 and Pa == 80
+    for order, start, key in ((ix["cam_order"], ix["cam_start"], prob["camIdx"]),
+                              (ix["pt_order"], ix["pt_start"], prob["ptIdx"])):
+        assert sorted(order) == list(range(257))
+        for a in range(len(start) - 1):
+            seg = order[start[a]:start[a + 1]]
+            assert len(seg) >= 1 and len(set(key[seg])) == 1 and (np.diff(seg) > 0).all()
+    # the duplicated (camera, point) pair: observations 0 and 256, in that order, on both sides
+    seg = ix["pt_order"][ix["pt_start"][list(ix["act_pts"]).index(prob["ptIdx"][0])]:]
+    assert seg[0] == 0 and 256 in seg[:ix["pt_start"][1] - ix["pt_start"][0] + 40]
+
+
+def test_build_index_skips_idle_cameras_and_points():
+    prob = synthetic.make_ba_problem(2, 40, 300, 900, active_cams=21, observed_points=280)
+    ix, A, Pa = _check_index(prob, 40, 300)
+    assert A == 21 and Pa == 280
+    assert np.array_equal(ix["act_cams"], np.unique(prob["camIdx"]))
+    one = synthetic.make_ba_problem(0, 1, 1, 1)
+    _check_index(one, 1, 1)
+    _check_index(one, 3, 2)   # the same single observation among idle variables
+
+
+def test_build_index_refusals(lib):
+    err = lambda: lib.onepose_last_error().decode()
+    pt = np.array([0, 1, 2, 1], dtype=np.int64)
+    cam = np.array([0, 0, 1, 1], dtype=np.int64)
+    nb = lib.onepose_ba_index_bytes(4, 2, 3)
+    assert nb > 0
+    buf = np.zeros(nb, dtype=np.uint8)
+    a, pa = ctypes.c_int(-1), ctypes.c_int(-1)
+
+    def call(pt=pt, cam=cam, n=4, C=2, P=3, out=buf, nbytes=nb, pa_ref=ctypes.byref(pa)):
+        return lib.onepose_ba_build_index(None if pt is None else pt.ctypes.data,
+                                          None if cam is None else cam.ctypes.data, n, C, P,
+                                          None if out is None else out.ctypes.data, nbytes,
+                                          ctypes.byref(a), pa_ref)
+
+    assert call() == OK and (a.value, pa.value) == (2, 3)
+    for kw in ({"pt": None}, {"cam": None}, {"out": None}, {"pa_ref": None}):
+        assert call(**kw) == INVALID and "null" in err(), kw
+    for kw in ({"n": 0}, {"C": 0}, {"P": 0}, {"n": (1 << 20) + 1}, {"C": -1}):
+        assert call(**kw) == INVALID and "n_obs" in err(), kw
+    assert call(nbytes=nb - 1) == WORKSPACE and "needed" in err()
+    for bad_pt, bad_cam in ((3, 0), (-1, 0), (0, 2), (0, -1), (1 << 40, 0)):
+        p2, c2 = pt.copy(), cam.copy()
+        p2[2], c2[2] = bad_pt, bad_cam
+        assert call(pt=p2, cam=c2) == INVALID and "observation 2" in err()
+        with pytest.raises(_lib.OnePoseError):
+            tracker.build_index(p2, c2, 2, 3)
+    # order: null, shape, buffer size, ids
+    p2 = pt.copy()
+    p2[0] = 9
+    assert call(pt=p2, nbytes=0) == WORKSPACE
+    assert call(pt=p2, n=0, nbytes=0) == INVALID and "n_obs" in err()
+    for bad in ((0, 2, 3), (4, 0, 3), (4, 2, 0), (-1, 2, 3)):
+        assert lib.onepose_ba_index_bytes(*bad) == 0
+
+
+# ---- refusals of the device entry points (dummy pointers, never dereferenced) -------------------
+def _solve(lib, points=256, cam_pose=256, features=256, pt=256, cam=256, index=256, N=50, C=6,
+           P=20, A=6, Pa=20, iters=5, succ=5, radius=1e4, info=256, ws=256, ws_bytes=1 << 40):
+    return lib.onepose_ba_solve(points, cam_pose, features, pt, cam, index, N, C, P, A, Pa, iters,
+                                succ, radius, info, ws, ws_bytes, None)
+
+
+def test_solve_refusals(lib):
+    err = lambda: lib.onepose_last_error().decode()
+    for k in ("points", "cam_pose", "features", "pt", "cam", "index", "info", "ws"):
+        assert _solve(lib, **{k: None}) == INVALID and "null" in err(), k
+    for kw in ({"N": 0}, {"C": 0}, {"P": 0}, {"A": 0}, {"Pa": 0}, {"A": 7}, {"Pa": 21},
+               {"N": (1 << 20) + 1}, {"N": 5, "A": 6}):
+        assert _solve(lib, **kw) == INVALID and "shape" in err(), kw
+    lim = lib.onepose_ba_max_active_cameras()
+    assert _solve(lib, C=lim + 1, A=lim + 1, N=100) == INVALID and "active cameras" in err()
+    assert _solve(lib, C=lim, A=lim, N=100, ws_bytes=0) == WORKSPACE
+    for it in (0, 17, -1):
+        assert _solve(lib, iters=it) == INVALID and "max_iters" in err()
+    assert _solve(lib, iters=16, ws_bytes=0) == WORKSPACE and _solve(lib, iters=1, ws_bytes=0) == WORKSPACE
+    assert _solve(lib, succ=0) == INVALID and "max_success" in err()
+    for r in (0.0, -1.0, float("nan"), float("inf")):
+        assert _solve(lib, radius=r) == INVALID and "initial_radius" in err()
+    need = lib.onepose_ba_workspace_bytes(50, 6, 20)
+    assert need > 0
+    assert _solve(lib, ws_bytes=need - 1) == WORKSPACE and "needed" in err()
+
+
+def test_solve_refusals_come_in_the_documented_order(lib):
+    """null pointers, shapes, active cameras over the limit, max_iters, max_success, the radius,
+    then the workspace: a call wrong in several ways reports the first."""
+    err = lambda: lib.onepose_last_error().decode()
+    lim = lib.onepose_ba_max_active_cameras()
+    wrong = dict(points=None, N=0, iters=0, succ=0, radius=-1.0, ws_bytes=0)
+    assert _solve(lib, **wrong) == INVALID and "null" in err()
+    del wrong["points"]
+    assert _solve(lib, **wrong) == INVALID and "shape" in err()
+    wrong.update(N=100, C=lim + 1, A=lim + 1)
+    assert _solve(lib, **wrong) == INVALID and "active cameras" in err()
+    wrong.update(C=6, A=6)
+    for key, word in (("iters", "max_iters"), ("succ", "max_success"), ("radius", "radius")):
+        assert _solve(lib, **wrong) == INVALID and word in err(), (key, err())
+        del wrong[key]
+    assert _solve(lib, **wrong) == WORKSPACE
+
+
+def test_workspace_bytes(lib):
+    wb = lib.onepose_ba_workspace_bytes
+    lim = lib.onepose_ba_max_active_cameras()
+    for bad in ((0, 1, 1), (5, 0, 1), (5, 1, 0), (5, lim + 1, 1), ((1 << 20) + 1, 1, 1)):
+        assert wb(*bad) == 0, bad
+    prev = 0
+    for n in (1, 255, 256, 257, 4400):
+        cur = wb(n, min(n, lim), min(n, 300))
+        assert cur >= prev and cur > 0   # every array is carved at a 256-byte granule
+        prev = cur
+    assert wb(4400, lim, 300) > wb(257, lim, 257) > wb(1, 1, 1)
+
+
+def test_linearize_and_triangulate_refusals(lib):
+    err = lambda: lib.onepose_last_error().decode()
+    args = [256] * 5 + [10, 2, 3] + [256] * 4 + [None]
+    for i in (0, 1, 2, 3, 4, 8, 9, 10, 11):
+        a = list(args)
+        a[i] = None
+        assert lib.onepose_ba_linearize(*a) == INVALID and "null" in err(), i
+    for i, v in ((5, 0), (6, 0), (7, 0), (5, (1 << 20) + 1)):
+        a = list(args)
+        a[i] = v
+        assert lib.onepose_ba_linearize(*a) == INVALID and "shape" in err(), i
+    a[0] = None   # null comes first
+    assert lib.onepose_ba_linearize(*a) == INVALID and "null" in err()
+    targs = [256] * 4 + [10, 20.0, 0.15] + [256] * 5 + [None]
+    for i in (0, 1, 2, 3, 7, 8, 9, 10, 11):
+        a = list(targs)
+        a[i] = None
+        assert lib.onepose_triangulate(*a) == INVALID and "null" in err(), i
+    for n in (0, -1, (1 << 24) + 1):
+        a = list(targs)
+        a[4] = n
+        assert lib.onepose_triangulate(*a) == INVALID and "n =" in err()
+    a = list(targs)
+    a[5] = float("nan")
+    assert lib.onepose_triangulate(*a) == INVALID and "NaN" in err()
+    a[4] = 0   # n before the thresholds
+    assert lib.onepose_triangulate(*a) == INVALID and "n =" in err()
+
+
+# ---- the Python layer -------------------------------------------------------------------------
+def _window_restatement(kpt2ds, kpt2d3d_ids, kpt2d_fids, cams, win_size):
+    """ba_tracker.py:362-370, line by line."""
+    valid2d_idx = np.where(kpt2d3d_ids != -1)[0]
+    if np.max(kpt2d_fids) > win_size:
+        valid_idx_fid = np.where(kpt2d_fids > np.max(kpt2d_fids) - win_size)
+        valid2d_idx = np.intersect1d(valid_idx_fid, valid2d_idx)
+    ks = cams[np.array(kpt2d_fids[valid2d_idx], dtype=int), 6:]
+    features = np.concatenate([kpt2ds[valid2d_idx], ks], axis=1)
+    return features, kpt2d3d_ids[valid2d_idx], kpt2d_fids[valid2d_idx]
+
+
+@pytest.mark.parametrize("n_frames,win", [(8, 10), (10, 10), (11, 10), (30, 20), (30, 10)])
+def test_window_rule_of_apply_ba(n_frames, win):
+    rs = np.random.RandomState(n_frames * 100 + win)
+    fids = np.repeat(np.arange(n_frames), 12).astype(np.float64)   # the reference keeps floats
+    ids = rs.randint(-1, 40, len(fids))
+    kpts = rs.uniform(0, 512, (len(fids), 2))
+    cams = rs.standard_normal((n_frames, 9))
+    f, p, c, valid = tracker.ba_window(kpts, ids, fids, cams, win)
+    rf, rp, rc = _window_restatement(kpts, ids, fids, cams, win)
+    assert np.array_equal(f, rf) and np.array_equal(p, rp) and np.array_equal(c, rc)
+    assert f.dtype == np.float64 and p.dtype == np.int64 and c.dtype == np.int64
+    assert (ids[valid] != -1).all()
+    if n_frames - 1 > win:
+        assert c.min() == n_frames - win and len(np.unique(c)) == win
+    else:
+        assert c.min() == 0
+
+
+def test_cpu_calls_raise():
+    prob = synthetic.make_ba_problem(0, 3, 7, 15)
+    t = {k: torch.from_numpy(v) for k, v in prob.items()}
+    with pytest.raises(RuntimeError, match="ROCm GPU"):
+        tracker.bundle_adjust(t["points"], t["cam_pose"], t["features"], t["ptIdx"], t["camIdx"])
+    with pytest.raises(RuntimeError, match="ROCm GPU"):
+        tracker.triangulate_points(torch.zeros(3, 4, dtype=torch.float64),
+                                   torch.zeros(3, 4, dtype=torch.float64),
+                                   torch.zeros(2, 2, dtype=torch.float64),
+                                   torch.zeros(2, 2, dtype=torch.float64))
+
+
+def test_cam_param_round_trip_and_project():
+    rs = np.random.RandomState(4)
+    for ang in (0.0, 1e-9, 0.3, 2.0, np.pi - 1e-6, np.pi):
+        ax = rs.standard_normal(3)
+        rvec = ax / np.linalg.norm(ax) * ang
+        K = np.array([[520.0, 0, 250.0], [0, 520.0, 260.0], [0, 0, 1]])
+        pose = np.eye(4)
+        pose[:3, :3] = tracker.rodrigues(rvec)
+        pose[:3, 3] = [0.1, -0.2, 9.0]   # the points stay in front of the camera
+        assert np.abs(pose[:3, :3] @ pose[:3, :3].T - np.eye(3)).max() < 1e-14
+        bal = tracker.get_cam_param(K, pose)
+        assert bal.shape == (9,) and np.array_equal(bal[6:], [520.0, 250.0, 260.0])
+        K2, pose2 = tracker.get_cam_params_back(bal)
+        assert np.array_equal(K2, K) and np.abs(pose2 - pose).max() < 1e-7
+        # the BAL vector drives the cost function: same pixels as project()
+        X = rs.uniform(-0.05, 0.05, (5, 3)) + [0, 0, 3.0]
+        uv = tracker.project(X, K, pose[:3])
+        feats = np.concatenate([uv, np.tile(bal[6:], (5, 1))], 1)
+        r = O.linearize(X, bal[None, :6], feats, np.arange(5), np.zeros(5, int), jac=False)
+        # (near pi the matrix-to-vector direction keeps about 1e-10 of the axis)
+        assert np.abs(r).max() < (1e-6 if ang > 3 else 1e-9)
