@@ -318,13 +318,17 @@ def _bn_stats(rs, sd, prefix, c):
     sd[f"{prefix}.num_batches_tracked"] = np.array(0, dtype=np.int64)
 
 
-def superglue_state_dict(seed: int = 0, well_conditioned: bool = True) -> dict[str, np.ndarray]:
+def superglue_state_dict(seed: int = 0, well_conditioned: bool = True, affine_bn: bool = False,
+                         bin_score: float = 1.0) -> dict[str, np.ndarray]:
     """A full ``SuperGlue`` state dict with the reference's keys and shapes (superglue.py:247-262):
     torch-default conv initialisation, randomised BatchNorm running statistics; with
     ``well_conditioned`` the last conv of every layer's MLP is scaled by 0.3 and ``final_proj``
-    is 20 x a random orthogonal matrix with zero bias, so the matcher produces real matches."""
+    is 20 x a random orthogonal matrix with zero bias, so the matcher produces real matches.
+    With ``affine_bn`` every BatchNorm gets a trained-like affine part, gamma ~ U(0.5, 1.5) and
+    beta ~ 0.1 N(0, 1), drawn from a stream of their own (every other tensor is what it is without
+    the flag); ``bin_score`` is the dustbin score (the trained value is about 2.37)."""
     rs = np.random.RandomState(seed)
-    sd: dict[str, np.ndarray] = {"bin_score": np.array(1.0, dtype=np.float32)}
+    sd: dict[str, np.ndarray] = {"bin_score": np.array(bin_score, dtype=np.float32)}
     chans = [3, *SUPERGLUE_KENC, DESC_DIM]
     for j in range(len(chans) - 1):
         w, b = _conv_default(rs, chans[j + 1], chans[j])
@@ -355,6 +359,13 @@ def superglue_state_dict(seed: int = 0, well_conditioned: bool = True) -> dict[s
         w = (20.0 * q).astype(np.float32)[:, :, None]
         b = np.zeros(DESC_DIM, np.float32)
     sd["final_proj.weight"], sd["final_proj.bias"] = w, b
+    if affine_bn:
+        ra = np.random.RandomState([seed, 0xB17])
+        for k in [k for k in sd if k.endswith(".running_mean")]:
+            p = k[: -len(".running_mean")]
+            c = sd[k].shape[0]
+            sd[f"{p}.weight"] = ra.uniform(0.5, 1.5, size=c).astype(np.float32)
+            sd[f"{p}.bias"] = (0.1 * ra.standard_normal(c)).astype(np.float32)
     return sd
 
 
@@ -373,10 +384,13 @@ def _sg_derive(rs, kp, desc, n):
 
 
 def make_superglue_inputs(n0: int, n1: int, seed: int = 0, batch: int = 1,
-                          shared1: bool = False) -> dict[str, np.ndarray]:
+                          shared1: bool = False, image_hw0=(SUPERGLUE_IMAGE, SUPERGLUE_IMAGE),
+                          image_hw1=(SUPERGLUE_IMAGE, SUPERGLUE_IMAGE)) -> dict[str, np.ndarray]:
     """The reference's ``data`` dict for ``SuperGlue.forward`` (superglue.py:264-284) as float32
     numpy: descriptors0/1 [B,256,n], keypoints0/1 [B,n,2], scores0/1 [B,n], image0/1 (only their
-    shape is read: 512 x 512).  Image 1's points are another view of image 0's (``_sg_derive``).
+    shape is read: ``image_hw0`` / ``image_hw1`` = (h, w), 512 x 512 by default).  Image 1's
+    points are another view of image 0's (``_sg_derive``).  The points are drawn in the 512 x 512
+    square and then scaled to each image's (h, w).
     With ``shared1`` image 1 is one set for the whole batch (made from sample 0's image 0; the
     other samples' image 0 are views of it) and is returned with batch dimension 1."""
     rs = np.random.RandomState(seed)
@@ -395,15 +409,21 @@ def make_superglue_inputs(n0: int, n1: int, seed: int = 0, batch: int = 1,
             d1.append(dd1)
     b1 = len(kp1)
     f32 = np.float32
+    kp0, kp1 = np.stack(kp0), np.stack(kp1)
+    (h0, w0), (h1, w1) = image_hw0, image_hw1
+    if (h0, w0) != (SUPERGLUE_IMAGE, SUPERGLUE_IMAGE):
+        kp0 = kp0 * (np.array([w0, h0], np.float64) / SUPERGLUE_IMAGE)
+    if (h1, w1) != (SUPERGLUE_IMAGE, SUPERGLUE_IMAGE):
+        kp1 = kp1 * (np.array([w1, h1], np.float64) / SUPERGLUE_IMAGE)
     return {
         "descriptors0": np.ascontiguousarray(np.stack(d0).transpose(0, 2, 1)).astype(f32),
         "descriptors1": np.ascontiguousarray(np.stack(d1).transpose(0, 2, 1)).astype(f32),
-        "keypoints0": np.stack(kp0).astype(f32),
-        "keypoints1": np.stack(kp1).astype(f32),
+        "keypoints0": kp0.astype(f32),
+        "keypoints1": kp1.astype(f32),
         "scores0": rs.uniform(0.01, 1.0, size=(batch, n0)).astype(f32),
         "scores1": rs.uniform(0.01, 1.0, size=(b1, n1)).astype(f32),
-        "image0": np.zeros((batch, 1, SUPERGLUE_IMAGE, SUPERGLUE_IMAGE), f32),
-        "image1": np.zeros((b1, 1, SUPERGLUE_IMAGE, SUPERGLUE_IMAGE), f32),
+        "image0": np.zeros((batch, 1, h0, w0), f32),
+        "image1": np.zeros((b1, 1, h1, w1), f32),
     }
 
 

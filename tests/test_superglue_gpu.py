@@ -16,7 +16,7 @@ import torch
 import parity
 import superglue_oracle as oracle
 from onepose_amd import _lib, superglue, synthetic
-from test_superglue_host import CASES, load_case
+from test_superglue_host import CASES, T_BIN_SCORE, load_case
 
 pytestmark = pytest.mark.gpu
 KEYS = ("matches0", "matches1", "matching_scores0", "matching_scores1")
@@ -220,7 +220,18 @@ def marginal_errors(Z, want, m, n):
 @pytest.mark.parametrize("m,n,iters,batch", [(1, 1, 1, 1), (1, 70, 20, 1), (65, 33, 20, 2),
                                              (257, 300, 100, 1), (64, 64, 0, 1)])
 def test_log_optimal_transport_against_oracle(device, m, n, iters, batch):
-    alpha = 1.0
+    check_lot(device, m, n, iters, batch, 1.0)
+
+
+@pytest.mark.parametrize("alpha", [2.3457, -1.5])
+@pytest.mark.parametrize("m,n,iters", [(255, 33, 20), (256, 33, 20), (256, 64, 20)])
+def test_log_optimal_transport_chunk_boundary(device, m, n, iters, alpha):
+    """m + 1 = 256 rows are one column-pass chunk, 257 are three (128, 128 and the dustbin row
+    alone); a trained-like and a negative dustbin score."""
+    check_lot(device, m, n, iters, 1, alpha)
+
+
+def check_lot(device, m, n, iters, batch, alpha):
     S = np.stack([lot_scores(m, n)] + [lot_scores(m + 3, n + 5)[3:, 5:] for _ in range(batch - 1)])
     got = gpu_lot(device, S, alpha, iters)
     assert np.isfinite(got).all()
@@ -239,16 +250,33 @@ def test_log_optimal_transport_against_oracle(device, m, n, iters, batch):
 
 
 # ---------------------------------------------------------------- 4. layer states
+# trained-like weights, images 480 x 640 and 384 x 512, (n0, n1, input seed): below one encoder
+# group, tile edges at 64 -+ 1, and 256 tokens against 40 (the seeds of the same shapes in
+# test_superglue_edges_gpu.py)
+RAGGED = ((7, 9, 0), (63, 65, 0), (256, 40, 0))
+
+
 def test_final_descriptors_through_scores(device):
     """sinkhorn_iters = 0: log_assignment's inner block is S - norm, S = mdesc0 . mdesc1 / 16, the
     end of the encoder and all 18 layers and the final projection.  fp32 yardstick: the oracle's
-    own formulas evaluated in float32 (numpy)."""
+    own formulas evaluated in float32 (numpy).  superglue_m's inputs, then the ragged shapes."""
     g, sd, data = case("superglue_m")
-    want = oracle_m()
-    with oracle.precision(np.float32):
+    check_scores_through_layers(device, "superglue_m", sd, data, oracle_m())
+    tsd = synthetic.superglue_state_dict(11, affine_bn=True, bin_score=T_BIN_SCORE)
+    for n0, n1, seed in RAGGED:
+        data = synthetic.make_superglue_inputs(n0, n1, seed=seed, image_hw0=(480, 640),
+                                               image_hw1=(384, 512))
+        check_scores_through_layers(device, f"{n0}x{n1}", tsd, data,
+                                    oracle.forward(tsd, data, iters=0, keep_states=True))
+
+
+def check_scores_through_layers(device, what, sd, data, want):
+    # (without Sinkhorn the fp32 matching scores exp(S - norm) overflow; they are not used)
+    with oracle.precision(np.float32), np.errstate(over="ignore"):
         cpu = oracle.forward(sd, data, iters=0, keep_states=True)
     out = run(model_for(sd, device, 0), to_dev(data, device))
     n0, n1 = want["scores"].shape[1:]
+    assert out["log_assignment"].shape == (1, n0 + 1, n1 + 1)
     norm = -np.log(n0 + n1)
     S = np.float64(out["log_assignment"][0][:-1, :-1]) + norm
     e_gpu = np.abs(S - want["scores"][0]).max()
@@ -256,12 +284,14 @@ def test_final_descriptors_through_scores(device):
     # the CPU's S, which never carried norm: put the CPU's S through the same round trip)
     cpu_S = np.float64(np.float32(cpu["scores"][0]) - np.float32(norm)) + norm
     e_cpu = np.abs(cpu_S - want["scores"][0]).max()
-    print(f"scores after 18 layers: gpu error {e_gpu:.3g}, cpu fp32 error {e_cpu:.3g}, "
+    print(f"{what} scores after 18 layers: gpu error {e_gpu:.3g}, cpu fp32 error {e_cpu:.3g}, "
           f"max |S| {np.abs(want['scores']).max():.3g}")
     assert e_gpu <= 4 * e_cpu
-    # the dustbins carry bin_score - norm
-    assert np.allclose(out["log_assignment"][0][-1, :], 1.0 - norm, rtol=0, atol=1e-6)
-    assert np.allclose(out["log_assignment"][0][:, -1], 1.0 - norm, rtol=0, atol=1e-6)
+    # the dustbins carry bin_score - norm: the model's fp32 bin_score, the subtraction in float64,
+    # rounded to fp32 once
+    bins = np.float32(np.float64(np.float32(sd["bin_score"])) - norm)
+    assert np.allclose(out["log_assignment"][0][-1, :], bins, rtol=0, atol=1e-6)
+    assert np.allclose(out["log_assignment"][0][:, -1], bins, rtol=0, atol=1e-6)
 
 
 # ---------------------------------------------------------------- 5. determinism, reentrancy
