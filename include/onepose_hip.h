@@ -784,6 +784,101 @@ int onepose_triangulate(const double* P1, const double* P2, const double* pts1,
                         double* err1, double* err2, double* z, uint8_t* keep, void* stream);
 
 /* ------------------------------------------------------------------------------------ *
+ * Tracker front end  --  pyramidal Lucas-Kanade optical flow
+ *   onepose_lk_build_pyramid + onepose_lk_track replace cv2.calcOpticalFlowPyrLK as
+ *   BATracker.kpt_flow_track calls it (src/tracker/ba_tracker.py:113-126: 8-bit single-channel
+ *   images, winSize 15 x 15, maxLevel 2, criteria (EPS | COUNT, 10, 0.03), no flags).
+ * Versioned on its own: onepose_lk_version() returns 1; onepose_abi_version() was not bumped.
+ * Not produced: cv2's err output (the reference discards it).  Not supported:
+ * OPTFLOW_USE_INITIAL_FLOW, OPTFLOW_LK_GET_MIN_EIGENVALS, multi-channel or non-8-bit images,
+ * non-square windows.
+ *
+ * No OpenCV source or binary is at hand, so parity with cv2 itself is NOT verified; what is
+ * assumed about OpenCV 4.4 is listed in DESIGN.md.  The contract below is what the kernels
+ * compute; tests/lk_oracle.py restates it in numpy and the GPU tests ask for equal bits.
+ *
+ * Limits, checked on the host before any launch (a _bytes / _levels query returns 0 for an
+ * unsupported shape, the other entry points ONEPOSE_ERR_INVALID):  win odd, 3 <= win <= 31;
+ * 0 <= max_level <= 5;  win < h, w <= 8192;  1 <= batch <= 65535;  0 <= max_points <= 2^24
+ * (max_points == 0 is a no-op that returns 0);  max_count is clamped to [0, 100] and epsilon to
+ * [0, 10] and then squared (in double, rounded to float once), as cv2 does;  NaN epsilon or
+ * min_eig_threshold is refused;  a batch stride is 0 (shared) or at least one item.  counts is a
+ * device array, so the host cannot see it: the kernel clamps counts[b] to [0, max_points].
+ *
+ * The pyramid blob (onepose_lk_pyramid_bytes per image, a multiple of 256): per level, the image
+ * uint8 [lh, lw] and then the derivative int16 [lh, lw, 2] (dx, dy interleaved), each at a
+ * 256-byte-aligned offset that onepose_lk_pyramid_layout (a host function) reports, so a level
+ * is a plain view of the blob.  No border is stored.  The derivative space is reserved but not
+ * written with with_deriv == 0 (the next image of a pair needs none).  Two launches per call:
+ * level 0 with its derivative and level 1 from the image; then levels >= 1 by one workgroup per
+ * image (skipped when nothing is left for it).  Images of more than 1024 x 1024 pixels get one
+ * grid launch per level >= 1 in place of that workgroup.
+ *
+ * pyrDown: [1 4 6 4 1] horizontally then vertically in integers, output ((h+1)/2, (w+1)/2),
+ *   output (y, x) centred on (2y, 2x), source indices reflected (BORDER_REFLECT_101),
+ *   (sum + 128) >> 8.
+ * Levels: level l + 1 is built only while l < max_level and its width and height both exceed
+ *   win; onepose_lk_levels returns the number built (>= 1).
+ * Scharr: rows reflected-101 inside the level, t0 = (up + down) * 3 + cur * 10, t1 = down - up;
+ *   columns reflected-101, dx = t0[x+1] - t0[x-1], dy = (t1[x+1] + t1[x-1]) * 3 + t1[x] * 10.
+ * Reads outside a level (up to win pixels): image reflected-101, derivative zero.
+ * Per point, per level l from the top down to 0, all floats fp32, every step a separate
+ * operation in this order (no fused multiply-add), sqrt and / correctly rounded:
+ *   prev = pts * (1 / (1 << l));  next = prev at the top level, else next = next * 2;
+ *   half = (win - 1) * 0.5;  p = prev - half;  ip = floor(p);
+ *   OUT(ip): ip.x < -win || ip.x >= cols || ip.y < -win || ip.y >= rows, decided by float
+ *     comparisons on floor(p) before any conversion to integer (NaN is OUT);
+ *   if OUT(ip): status = 0 if l == 0; go to the next level;
+ *   a = p.x - ip.x, b = p.y - ip.y;  iw00 = rint((1-a)(1-b) 2^14), iw01 = rint(a (1-b) 2^14),
+ *   iw10 = rint((1-a) b 2^14), iw11 = 2^14 - iw00 - iw01 - iw10 (round half to even);
+ *   descale(v, n) = (v + (1 << (n-1))) >> n;  over the win x win window at ip:
+ *   I = descale(4-tap image sum, 9);  Ix, Iy = descale(4-tap derivative sum, 14);
+ *   A11, A12, A22 = the exact integer sums of Ix^2, Ix Iy, Iy^2, each converted to float once
+ *     (round to nearest even) and multiplied by 2^-20;
+ *   D = A11 A22 - A12 A12;
+ *   minEig = (A22 + A11 - sqrt((A11 - A22)(A11 - A22) + 4 A12 A12)) / (2 win^2);
+ *   if minEig < min_eig_threshold || D < FLT_EPSILON: status = 0 if l == 0; next level;
+ *   Dinv = 1 / D;  n = next - half;  prevDelta = 0;  up to max_count times (j = 0, 1, ...):
+ *     if OUT(floor(n)): status = 0 if l == 0; break;
+ *     weights from n;  diff = descale(4-tap sum of the next image, 9) - I;
+ *     b1, b2 = the exact integer sums of diff Ix, diff Iy, converted once, times 2^-20;
+ *     delta = ((A12 b2 - A22 b1) Dinv, (A12 b1 - A11 b2) Dinv);  n += delta;  next = n + half;
+ *     if delta.x delta.x + delta.y delta.y <= epsilon^2: break;
+ *     if j > 0 && |delta.x + prevDelta.x| < 0.01 && |delta.y + prevDelta.y| < 0.01:
+ *       next -= delta * 0.5; break;
+ *     prevDelta = delta.
+ *   status starts at 1; next_pts = next after level 0.
+ * The sums are integers reduced across the wave, so the result does not depend on the lane
+ * mapping or the summation order and is bit-identical from run to run (cv2 accumulates the same
+ * terms in float, in an order that depends on its SIMD path: a stated difference of at most
+ * rounding).
+ * A point that is NaN, infinite or of magnitude >= 2^30 gets status 0 and next_pts = prev_pts,
+ * bit for bit, before anything is computed from it (the rule above gives the same result for
+ * the finite ones; this spares them the arithmetic).
+ *
+ * onepose_lk_track: one wave per point, four points per 256-thread workgroup, one launch.
+ * prev_pyr (prev_pyr_bstride BYTES per item, 0 = shared) needs its derivatives; next_pyr
+ * [batch x pyramid_bytes];  prev_pts [.., max_points, 2] fp32 (prev_pts_bstride FLOATS per item,
+ * 0 = shared);  next_pts [batch, max_points, 2], status [batch, max_points]: rows from
+ * counts[b] on are not written.  No entry point allocates, frees or synchronises; all can be
+ * captured in a graph.  All pointers are device pointers except the four outputs of
+ * onepose_lk_pyramid_layout.
+ * ------------------------------------------------------------------------------------ */
+int onepose_lk_version(void);
+int onepose_lk_levels(int h, int w, int win, int max_level);
+size_t onepose_lk_pyramid_bytes(int h, int w, int win, int max_level);
+int onepose_lk_pyramid_layout(int h, int w, int win, int max_level, int level, int* lh, int* lw,
+                              int64_t* image_offset, int64_t* deriv_offset);
+int onepose_lk_build_pyramid(const uint8_t* image, int64_t image_bstride, int batch, int h, int w,
+                             int win, int max_level, int with_deriv, void* pyramids,
+                             void* stream);
+int onepose_lk_track(const void* prev_pyr, int64_t prev_pyr_bstride, const void* next_pyr,
+                     const float* prev_pts, int64_t prev_pts_bstride, const int* counts, int batch,
+                     int max_points, int h, int w, int win, int max_level, int max_count,
+                     float epsilon, float min_eig_threshold, float* next_pts, uint8_t* status,
+                     void* stream);
+
+/* ------------------------------------------------------------------------------------ *
  * Measurement hook (bench.py's roofline). While enabled, every launch whose kernel kind
  * is in `kind_mask` (bit k = kind k, names from onepose_profile_kind_name) is bracketed by
  * two HIP events recorded on the launch's own stream.  Host-side state, not for use during

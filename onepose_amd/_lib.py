@@ -190,6 +190,17 @@ PROTOTYPES = {
     "onepose_triangulate": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_double,
                                     c_double, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                     c_void_p]),
+    "onepose_lk_version": (c_int, []),
+    "onepose_lk_levels": (c_int, [c_int, c_int, c_int, c_int]),
+    "onepose_lk_pyramid_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
+    "onepose_lk_pyramid_layout": (c_int, [c_int, c_int, c_int, c_int, c_int,
+                                          ctypes.POINTER(c_int), ctypes.POINTER(c_int),
+                                          ctypes.POINTER(c_int64), ctypes.POINTER(c_int64)]),
+    "onepose_lk_build_pyramid": (c_int, [c_void_p, c_int64, c_int, c_int, c_int, c_int, c_int,
+                                         c_int, c_void_p, c_void_p]),
+    "onepose_lk_track": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_int,
+                                 c_int, c_int, c_int, c_int, c_int, c_int, c_float, c_float,
+                                 c_void_p, c_void_p, c_void_p]),
     "onepose_profile_begin": (c_int, [ctypes.c_uint64, c_int]),
     "onepose_profile_begin_device": (c_int, [ctypes.c_uint64]),
     "onepose_profile_end_device": (c_int, [c_void_p, c_void_p, c_int]),

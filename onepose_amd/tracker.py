@@ -1,5 +1,14 @@
-"""The numeric stages of ``BATracker.track_ba`` (src/tracker/ba_tracker.py) after matching and
-PnP, on libonepose_hip (MI355X): bundle adjustment and triangulation, float64.
+"""The numeric stages of ``BATracker.track`` (src/tracker/ba_tracker.py) on libonepose_hip
+(MI355X): the front half that produces ``pose_init`` (pyramidal Lucas-Kanade optical flow, the
+flow -> PnP -> accept chain, motion prediction) and the back half after matching and PnP (bundle
+adjustment and triangulation, float64).
+
+* ``build_lk_pyramid`` / ``lk_track`` / ``calc_optical_flow_pyr_lk`` stand where the reference
+  calls ``cv2.calcOpticalFlowPyrLK`` (:113-126); include/onepose_hip.h states the arithmetic
+  (cv2 is not available here, so parity with it is pinned by known-answer scenes only).
+* ``kpt_flow_track`` (:113-126), ``flow_track`` (:295-356 without the drawing),
+  ``motion_prediction`` (:275-293), ``select_pose_init`` (:742-750), ``cm_degree_5_metric``
+  (:105-111), ``mat2euler`` / ``euler2mat`` (transforms3d's default 'sxyz' convention).
 
 * ``bundle_adjust`` stands where the reference calls DeepLM's ``Solve`` (:401-407): same
   arguments, variables updated in place.  The cost function is the reference's
@@ -13,8 +22,9 @@ PnP, on libonepose_hip (MI355X): bundle adjustment and triangulation, float64.
 * ``get_cam_param`` / ``get_cam_params_back`` (:443-466) with Rodrigues in numpy, ``project``
   (tracking_utils.py:74-88).
 
-The ``BATracker`` class itself, LK optical flow and motion prediction are not part of this
-package.  There is no CPU path: the GPU entry points raise on CPU tensors.
+Every numeric stage of ``track`` is here; the ``BATracker`` class itself (``add_kf``,
+``update_kf``, ``track_ba``'s bookkeeping) is not part of this package.  There is no CPU path:
+the GPU entry points raise on CPU tensors.
 """
 from __future__ import annotations
 
@@ -247,3 +257,309 @@ def project(xyz, K, RT, need_depth=False):
     xyz = np.dot(xyz, K.T)
     xy = xyz[:, :2] / xyz[:, 2:]
     return (xy, depth) if need_depth else xy
+
+
+# ---- the front half of BATracker.track: optical flow, flow_track, motion prediction ----
+
+LK_VERSION = 1
+TERM_CRITERIA_COUNT, TERM_CRITERIA_EPS = 1, 2   # cv2.TERM_CRITERIA_*
+
+
+class LKPyramid:
+    """The blob(s) of ``onepose_lk_build_pyramid`` with the shape they were built for: ``blob``
+    uint8 [B, pyramid_bytes] on the device.  ``level(l)`` gives plain views of it."""
+
+    def __init__(self, blob, h, w, win, max_level, with_deriv):
+        self.blob, self.h, self.w, self.win, self.max_level = blob, h, w, win, max_level
+        self.with_deriv = bool(with_deriv)
+        self.levels = _lib.load().onepose_lk_levels(h, w, win, max_level)
+
+    @property
+    def batch(self):
+        return self.blob.shape[0]
+
+    def level(self, l):
+        """(image uint8 [B, lh, lw], derivative int16 [B, lh, lw, 2]) of level ``l``."""
+        lh, lw, io, do = lk_pyramid_layout(self.h, self.w, self.win, self.max_level, l)
+        img = self.blob[:, io:io + lh * lw].view(self.batch, lh, lw)
+        der = self.blob[:, do:do + lh * lw * 4].view(torch.int16).view(self.batch, lh, lw, 2)
+        return img, der
+
+
+def lk_pyramid_layout(h, w, win, max_level, level):
+    """onepose_lk_pyramid_layout (a host function): (lh, lw, image offset, derivative offset)."""
+    lh, lw = ctypes.c_int(0), ctypes.c_int(0)
+    io, do = ctypes.c_int64(0), ctypes.c_int64(0)
+    _lib.check(_lib.load().onepose_lk_pyramid_layout(h, w, win, max_level, level,
+                                                     ctypes.byref(lh), ctypes.byref(lw),
+                                                     ctypes.byref(io), ctypes.byref(do)),
+               "onepose_lk_pyramid_layout")
+    return int(lh.value), int(lw.value), int(io.value), int(do.value)
+
+
+def build_lk_pyramid(image_u8, win=15, max_level=2, with_deriv=True):
+    """The image pyramid (and, with ``with_deriv``, its Scharr derivatives) of a CUDA uint8 image
+    ``[h, w]`` or batch ``[B, h, w]`` -> ``LKPyramid``.  Build a keyframe's once and reuse it for
+    every frame tracked against it; the second image of a pair needs no derivatives."""
+    if not isinstance(image_u8, torch.Tensor) or image_u8.dtype != torch.uint8 \
+            or image_u8.dim() not in (2, 3):
+        raise ValueError("build_lk_pyramid: expected a uint8 tensor [h, w] or [B, h, w]")
+    _need_gpu(image_u8)
+    img = image_u8[None] if image_u8.dim() == 2 else image_u8
+    img = img.contiguous()
+    B, h, w = img.shape
+    lib = _lib.load()
+    nbytes = lib.onepose_lk_pyramid_bytes(h, w, int(win), int(max_level))
+    if nbytes == 0 or B == 0:
+        raise ValueError(f"build_lk_pyramid: unsupported h={h} w={w} win={win} "
+                         f"max_level={max_level} (win odd in 3..31, max_level in 0..5, "
+                         "win < h, w <= 8192)")
+    dev = img.device
+    with torch.cuda.device(dev):
+        blob = torch.empty(B, nbytes, dtype=torch.uint8, device=dev)
+        _lib.check(lib.onepose_lk_build_pyramid(img.data_ptr(), h * w, B, h, w, int(win),
+                                                int(max_level), int(bool(with_deriv)),
+                                                blob.data_ptr(), _lib.stream_ptr(dev)),
+                   "onepose_lk_build_pyramid")
+    return LKPyramid(blob, h, w, int(win), int(max_level), with_deriv)
+
+
+def lk_track(prev_pyr, next_pyr, prev_pts, counts=None, max_count=10, epsilon=0.03,
+             min_eig_threshold=1e-4):
+    """onepose_lk_track: ``prev_pts`` CUDA float32 ``[n, 2]`` or ``[B, n, 2]`` tracked from
+    ``prev_pyr`` (built with derivatives) into each image of ``next_pyr`` -> ``(next_pts
+    [B, n, 2] float32, status [B, n] uint8)`` with B = ``next_pyr.batch``.  A ``prev_pyr`` of one
+    image and 2-D ``prev_pts`` are shared by the batch.  ``counts`` (CUDA int32 [B]) limits the
+    points of each item; the rows beyond keep ``prev_pts`` and status 0."""
+    if not isinstance(prev_pyr, LKPyramid) or not isinstance(next_pyr, LKPyramid):
+        raise ValueError("lk_track: prev_pyr and next_pyr come from build_lk_pyramid")
+    if (prev_pyr.h, prev_pyr.w, prev_pyr.win, prev_pyr.max_level) != \
+            (next_pyr.h, next_pyr.w, next_pyr.win, next_pyr.max_level):
+        raise ValueError("lk_track: the two pyramids differ in shape, window or levels")
+    if not prev_pyr.with_deriv:
+        raise ValueError("lk_track: prev_pyr was built without derivatives")
+    if not isinstance(prev_pts, torch.Tensor) or prev_pts.dtype != torch.float32 \
+            or prev_pts.dim() not in (2, 3) or prev_pts.shape[-1] != 2:
+        raise ValueError("lk_track: prev_pts must be float32 [n, 2] or [B, n, 2]")
+    _need_gpu(prev_pts, prev_pyr.blob, next_pyr.blob)
+    B, n = next_pyr.batch, prev_pts.shape[-2]
+    if prev_pyr.batch not in (1, B):
+        raise ValueError(f"lk_track: prev_pyr holds {prev_pyr.batch} images, next_pyr {B}")
+    if prev_pts.dim() == 3 and prev_pts.shape[0] not in (1, B):
+        raise ValueError(f"lk_track: prev_pts holds {prev_pts.shape[0]} items, next_pyr {B}")
+    if counts is not None and (not isinstance(counts, torch.Tensor) or counts.dtype != torch.int32
+                               or tuple(counts.shape) != (B,)):
+        raise ValueError("lk_track: counts must be an int32 tensor [B]")
+    prev_pts = prev_pts.contiguous()
+    shared_pts = prev_pts.dim() == 2 or prev_pts.shape[0] == 1
+    dev = prev_pts.device
+    lib = _lib.load()
+    with torch.cuda.device(dev):
+        if counts is None:
+            counts = torch.full((B,), n, dtype=torch.int32, device=dev)
+            next_pts = torch.empty(B, n, 2, dtype=torch.float32, device=dev)
+            status = torch.empty(B, n, dtype=torch.uint8, device=dev)
+        else:
+            _need_gpu(counts)
+            next_pts = prev_pts.reshape(-1, n, 2).expand(B, n, 2).clone()
+            status = torch.zeros(B, n, dtype=torch.uint8, device=dev)
+        rc = lib.onepose_lk_track(prev_pyr.blob.data_ptr(),
+                                  0 if prev_pyr.batch == 1 else prev_pyr.blob.shape[1],
+                                  next_pyr.blob.data_ptr(), prev_pts.data_ptr(),
+                                  0 if shared_pts else 2 * n, counts.data_ptr(), B, n,
+                                  prev_pyr.h, prev_pyr.w, prev_pyr.win, prev_pyr.max_level,
+                                  int(max_count), float(epsilon), float(min_eig_threshold),
+                                  next_pts.data_ptr(), status.data_ptr(), _lib.stream_ptr(dev))
+        _lib.check(rc, "onepose_lk_track")
+    return next_pts, status
+
+
+def _lk_criteria(criteria):
+    """cv2's TermCriteria as calcOpticalFlowPyrLK reads it: without COUNT the count is 30,
+    without EPS the epsilon is 0.001."""
+    kind, count, eps = criteria
+    return (int(count) if int(kind) & TERM_CRITERIA_COUNT else 30,
+            float(eps) if int(kind) & TERM_CRITERIA_EPS else 0.001)
+
+
+def _as_gray_gpu(img, device, name):
+    if isinstance(img, np.ndarray):
+        if img.dtype != np.uint8 or img.ndim != 2:
+            raise ValueError(f"{name}: expected an 8-bit single-channel image [h, w], got "
+                             f"{img.dtype} {img.shape}")
+        return torch.from_numpy(np.ascontiguousarray(img)).to(device)
+    if not isinstance(img, torch.Tensor) or img.dtype != torch.uint8 or img.dim() != 2:
+        raise ValueError(f"{name}: expected an 8-bit single-channel image [h, w]")
+    _need_gpu(img)
+    return img
+
+
+def _check_win(winSize):
+    if len(winSize) != 2 or winSize[0] != winSize[1]:
+        raise ValueError(f"winSize {tuple(winSize)}: only square windows are supported")
+    return int(winSize[0])
+
+
+def calc_optical_flow_pyr_lk(prev_img, next_img, prev_pts, winSize=(15, 15), maxLevel=2,
+                             criteria=(3, 10, 0.03), minEigThreshold=1e-4, kf_pyramid=None,
+                             device="cuda"):
+    """``cv2.calcOpticalFlowPyrLK(prev_img, next_img, prev_pts, None, winSize=, maxLevel=,
+    criteria=, minEigThreshold=)`` -> ``(next_pts [n, 1, 2] float32, status [n, 1] uint8,
+    None)``: numpy in gives numpy out, CUDA tensors in give CUDA tensors out.  ``prev_pts`` is
+    ``[n, 1, 2]`` or ``[n, 2]``.  cv2's ``err`` is not produced and its flags are not supported.
+    Two arguments are this package's own: ``kf_pyramid`` (an ``LKPyramid`` of ``prev_img`` with
+    derivatives, same window and levels) spares rebuilding it, and ``prev_img`` is then not
+    read; ``device`` is where numpy inputs are uploaded to (tensor inputs stay where they
+    are)."""
+    win = _check_win(winSize)
+    max_count, eps = _lk_criteria(criteria)
+    as_numpy = not isinstance(prev_pts, torch.Tensor)
+    if as_numpy:
+        if not torch.cuda.is_available():
+            raise RuntimeError("onepose_amd.tracker runs on a ROCm GPU only")
+        pts = np.ascontiguousarray(prev_pts, dtype=np.float32)
+        if pts.size % 2:
+            raise ValueError("prev_pts must be [n, 1, 2] or [n, 2]")
+        pts = torch.from_numpy(pts.reshape(-1, 2)).to(device)
+    else:
+        _need_gpu(prev_pts)
+        if prev_pts.dtype != torch.float32 or prev_pts.numel() % 2:
+            raise ValueError("prev_pts must be float32 [n, 1, 2] or [n, 2]")
+        pts = prev_pts.reshape(-1, 2)
+    dev = pts.device
+    nxt = build_lk_pyramid(_as_gray_gpu(next_img, dev, "next_img"), win, maxLevel, False)
+    if kf_pyramid is None:
+        kf_pyramid = build_lk_pyramid(_as_gray_gpu(prev_img, dev, "prev_img"), win, maxLevel, True)
+    n = pts.shape[0]
+    if n == 0:
+        out = torch.empty(0, 1, 2, dtype=torch.float32, device=dev)
+        st = torch.empty(0, 1, dtype=torch.uint8, device=dev)
+    else:
+        o, s = lk_track(kf_pyramid, nxt, pts, None, max_count, eps, minEigThreshold)
+        out, st = o.reshape(n, 1, 2), s.reshape(n, 1)
+    if as_numpy:
+        return out.cpu().numpy(), st.cpu().numpy(), None
+    return out, st, None
+
+
+def kpt_flow_track(im_kf, im_query, kpt2d_last, kf_pyramid=None):
+    """``BATracker.kpt_flow_track`` (:113-126): winSize 15 x 15, maxLevel 2, criteria (EPS | COUNT,
+    10, 0.03) -> ``(kpt_new [n, 2], valid_id)`` with ``valid_id`` the ``np.where`` tuple of status
+    == 1.  ``kf_pyramid``: the keyframe's ``build_lk_pyramid(im_kf)``, built once per keyframe."""
+    kpt_last = np.expand_dims(np.asarray(kpt2d_last, dtype=np.float32), axis=1)
+    kpt_new, status, _ = calc_optical_flow_pyr_lk(
+        im_kf, im_query, kpt_last, winSize=(15, 15), maxLevel=2,
+        criteria=(TERM_CRITERIA_EPS | TERM_CRITERIA_COUNT, 10, 0.03), kf_pyramid=kf_pyramid)
+    valid_id = np.where(status.flatten() == 1)
+    return np.squeeze(kpt_new, axis=1), valid_id
+
+
+def cm_degree_5_metric(pose_pred, pose_target):
+    """The tracker's pose distance (``BATracker.cm_degree_5_metric``, :105-111) between two
+    ``[3, 4]`` (or 4 x 4, first three rows) poses: (translation distance in cm, rotation angle in
+    degrees).  As in the reference the trace is limited from above only (and NaN counts as 3), so
+    a trace below -1 gives NaN."""
+    P, G = np.asarray(pose_pred)[:3], np.asarray(pose_target)[:3]
+    cm = 100 * np.linalg.norm(P[:, 3] - G[:, 3])
+    tr = (P[:, :3] @ G[:, :3].T).trace()
+    cos_angle = (tr - 1.0) / 2.0 if tr <= 3 else 1.0
+    return cm, np.degrees(np.arccos(cos_angle))
+
+
+ACCEPT_CM = ACCEPT_DEG = 7.0   # flow_track's acceptance rule (:351)
+ACCEPT_KPT_DIST = 10.0
+
+
+def flow_track(frame_info_dict, kf_frame_info):
+    """What ``BATracker.flow_track`` (:295-356) computes, without its drawing and timers: the
+    keyframe's ``mkpts2d`` are followed into the query image by optical flow, the points that
+    kept status 1 go with their ``mkpts3d`` through ``pose.ransac_PnP`` (``K_crop`` of the query,
+    scale 1), and the pose is judged by the mean reprojection distance of those points and by its
+    cm / degree distance to the query's ``pose_gt``.  Returns ``(pose_init_homo [4, 4], kpt_dist,
+    accepted)``; accepted means at most 7 cm and 7 degrees and ``kpt_dist`` below 10 px, and then
+    ``mkpts3d`` / ``mkpts2d`` (the tracked subset) are written into ``frame_info_dict``, which
+    the caller keeps as its ``last_kf_info``.
+
+    There is no image loader here: the caller puts the images themselves, uint8 ``[h, w]`` numpy
+    arrays or CUDA tensors, under the reference's key ``im_path`` of both dicts.  An optional
+    ``lk_pyramid`` entry of ``kf_frame_info`` is the keyframe's ``build_lk_pyramid`` result,
+    built once per keyframe."""
+    from . import pose as _pose
+    K = frame_info_dict["K_crop"]
+    tracked, keep = kpt_flow_track(kf_frame_info["im_path"], frame_info_dict["im_path"],
+                                   kf_frame_info["mkpts2d"], kf_frame_info.get("lk_pyramid"))
+    pts2d, pts3d = tracked[keep], kf_frame_info["mkpts3d"][keep]
+    pose34, pose44, _ = _pose.ransac_PnP(K, pts2d, pts3d)
+    residual = project(pts3d, K, pose34) - pts2d
+    kpt_dist = np.linalg.norm(residual, axis=1).mean()
+    cm, deg = cm_degree_5_metric(pose44, frame_info_dict["pose_gt"])
+    accepted = bool(cm <= ACCEPT_CM and deg <= ACCEPT_DEG and kpt_dist < ACCEPT_KPT_DIST)
+    if accepted:
+        frame_info_dict["mkpts3d"], frame_info_dict["mkpts2d"] = pts3d, pts2d
+    return pose44, kpt_dist, accepted
+
+
+_EULER_EPS4 = float(np.finfo(np.float64).eps) * 4.0
+
+
+def mat2euler(R):
+    """transforms3d.euler.mat2euler with its default axes 'sxyz': (ax, ay, az) with
+    R = Rz(az) Ry(ay) Rx(ax); at the gimbal lock (cy <= 4 eps) az = 0."""
+    R = np.asarray(R, dtype=np.float64)[:3, :3]
+    cy = np.hypot(R[0, 0], R[1, 0])
+    if cy > _EULER_EPS4:
+        ax = np.arctan2(R[2, 1], R[2, 2])
+        ay = np.arctan2(-R[2, 0], cy)
+        az = np.arctan2(R[1, 0], R[0, 0])
+    else:
+        ax = np.arctan2(-R[1, 2], R[1, 1])
+        ay = np.arctan2(-R[2, 0], cy)
+        az = 0.0
+    return float(ax), float(ay), float(az)
+
+
+def euler2mat(ax, ay, az):
+    """transforms3d.euler.euler2mat with its default axes 'sxyz': Rz(az) Ry(ay) Rx(ax)."""
+    cx, sx, cy, sy, cz, sz = np.cos(ax), np.sin(ax), np.cos(ay), np.sin(ay), np.cos(az), np.sin(az)
+    Rx = np.array([[1, 0, 0], [0, cx, -sx], [0, sx, cx]])
+    Ry = np.array([[cy, 0, sy], [0, 1, 0], [-sy, 0, cy]])
+    Rz = np.array([[cz, -sz, 0], [sz, cz, 0], [0, 0, 1]])
+    return Rz @ Ry @ Rx
+
+
+def motion_prediction(pose_list):
+    """Constant-velocity extrapolation of the last three 4 x 4 poses, as
+    ``BATracker.motion_prediction`` (:275-293) computes it: the translation of the last pose
+    advanced by the mean of the last two translation steps, and Euler angles ('sxyz') advanced
+    the same way.  The reference's quirk is kept: the angles it advances, its ``rot_t``, are
+    read from ``pose_list[-2]``, not ``[-1]`` (:285).  So the second angle step is zero, the
+    last pose's rotation never enters, and the result is the rotation of the pose before last
+    plus half the step that led to it."""
+    first, second, last = (np.asarray(p, dtype=np.float64) for p in pose_list[-3:])
+    t0, t1, t2 = first[:3, 3], second[:3, 3], last[:3, 3]
+    e0 = np.array(mat2euler(first))
+    e1 = np.array(mat2euler(second))
+    e2 = e1   # the quirk: not mat2euler(last)
+    out = np.eye(4)
+    out[:3, :3] = euler2mat(*(e2 + ((e1 - e0) + (e2 - e1)) / 2))
+    out[:3, 3] = t2 + ((t1 - t0) + (t2 - t1)) / 2
+    return out
+
+
+JUMP, LOST = 10.0, 20.0   # cm and degrees against the last pose (:742, :745)
+MAX_MOTION_FRAMES = 3
+
+
+def select_pose_init(pose_last, pose_ftk, kpt_dist, pose_mo, use_motion_cnt):
+    """Which pose starts the frame (``BATracker.track``, :734-750): the flow pose ``pose_ftk`` or
+    the motion-predicted ``pose_mo`` -> ``(pose_init, use_motion_cnt)``.  The flow pose is
+    measured against ``pose_last`` in cm / degrees.  A jump (more than 10 on either) is answered
+    with the motion pose for at most 3 frames in a row; a keypoint distance above 10 px always
+    is; otherwise the flow pose is taken while both distances are below 20, and the motion pose
+    beyond.  Taking the motion pose counts ``use_motion_cnt`` up, the flow pose resets it."""
+    cm, deg = cm_degree_5_metric(pose_last, pose_ftk)
+    jumped = cm > JUMP or deg > JUMP
+    distrust_flow = kpt_dist > ACCEPT_KPT_DIST or (jumped and use_motion_cnt < MAX_MOTION_FRAMES)
+    if not distrust_flow and cm < LOST and deg < LOST:
+        return pose_ftk, 0
+    return pose_mo, use_motion_cnt + 1
