@@ -1,7 +1,8 @@
 """The pyramidal Lucas-Kanade contract of include/onepose_hip.h restated in numpy: integer
 pyramids and derivatives, float32 steps one by one (numpy never fuses a multiply and an add), the
 window sums as exact integers.  Vectorised over the window; one Python loop over points, levels
-and iterations.  The GPU tests compare bits with this; tests/golden/lk.npz pins it."""
+and iterations.  The GPU tests compare bits with this; tests/golden/lk.npz and lk_edges.npz pin
+it, and tests/lk_model.py (float64, no fixed point, no code shared) is held against it."""
 import numpy as np
 
 F = np.float32
@@ -84,10 +85,24 @@ def eps_squared(epsilon):
     return F(e * e)
 
 
-def track(prev_pyr, next_pyr, pts, win, max_count=10, epsilon=0.03, min_eig=1e-4, eig_out=None):
+def exact_sum(v):
+    """The window sum as a Python int (the terms are int64 and far from its limits)."""
+    return int(v.sum())
+
+
+def wrapped_int32_sum(v):
+    """What a 32-bit accumulator would hold: every term fits int32, the sum wraps.  Not the
+    contract; tests pass it as ``window_sum`` to show which scenes tell the two apart."""
+    return int(v.astype(np.int32).sum(dtype=np.int32))
+
+
+def track(prev_pyr, next_pyr, pts, win, max_count=10, epsilon=0.03, min_eig=1e-4, eig_out=None,
+          trace=None, window_sum=exact_sum, stats=None):
     """-> next_pts [n, 2] float32, status [n] uint8, reason [n] int (how level 0 ended).
     ``eig_out`` (a dict) receives {point index: minEig at level 0} of the points that reach the
-    eigenvalue test there."""
+    eigenvalue test there.  ``trace`` (a list) receives (point, level, reason) for every level a
+    point visits, from the top down; a hostile point visits none.  ``stats`` (a dict) receives
+    under "max_ix2" the largest window sum of Ix^2 or Iy^2 met, as an exact integer."""
     pts = np.asarray(pts, dtype=np.float32).reshape(-1, 2)
     n, levels = len(pts), len(prev_pyr)
     max_count = min(max(int(max_count), 0), 100)
@@ -99,6 +114,7 @@ def track(prev_pyr, next_pyr, pts, win, max_count=10, epsilon=0.03, min_eig=1e-4
     out = np.zeros((n, 2), np.float32)
     status = np.ones(n, np.uint8)
     reason = np.full(n, -1, np.int64)
+    note = trace.append if trace is not None else (lambda t: None)
     with np.errstate(all="ignore"):
         for i in range(n):
             px, py = pts[i]
@@ -119,6 +135,7 @@ def track(prev_pyr, next_pyr, pts, win, max_count=10, epsilon=0.03, min_eig=1e-4
                 if _out(fx, fy, win, cols, rows):
                     if l == 0:
                         status[i], reason[i] = 0, R_OOB_PRE
+                    note((i, l, R_OOB_PRE))
                     continue
                 ix, iy = int(fx), int(fy)
                 wts = _weights(qx - fx, qy - fy)
@@ -126,9 +143,12 @@ def track(prev_pyr, next_pyr, pts, win, max_count=10, epsilon=0.03, min_eig=1e-4
                 Ix = (_tap(pder[l][..., 0], win, ix, iy, win, wts) + 8192) >> 14
                 Iy = (_tap(pder[l][..., 1], win, ix, iy, win, wts) + 8192) >> 14
                 scale = F(2.0 ** -20)
-                A11 = F(int((Ix * Ix).sum())) * scale
-                A12 = F(int((Ix * Iy).sum())) * scale
-                A22 = F(int((Iy * Iy).sum())) * scale
+                A11 = F(window_sum(Ix * Ix)) * scale
+                A12 = F(window_sum(Ix * Iy)) * scale
+                A22 = F(window_sum(Iy * Iy)) * scale
+                if stats is not None:
+                    stats["max_ix2"] = max(stats.get("max_ix2", 0), int((Ix * Ix).sum()),
+                                           int((Iy * Iy).sum()))
                 D = A11 * A22 - A12 * A12
                 dif = A11 - A22
                 m = (A22 + A11 - np.sqrt(dif * dif + F(4) * A12 * A12)) / F(2 * win * win)
@@ -137,6 +157,7 @@ def track(prev_pyr, next_pyr, pts, win, max_count=10, epsilon=0.03, min_eig=1e-4
                 if m < min_eig or D < FLT_EPSILON:
                     if l == 0:
                         status[i], reason[i] = 0, R_EIG
+                    note((i, l, R_EIG))
                     continue
                 Dinv = F(1) / D
                 nx, ny = ox - half, oy - half
@@ -151,8 +172,8 @@ def track(prev_pyr, next_pyr, pts, win, max_count=10, epsilon=0.03, min_eig=1e-4
                         break
                     wts = _weights(nx - fx, ny - fy)
                     diff = ((_tap(nimg[l], win, int(fx), int(fy), win, wts) + 256) >> 9) - I
-                    b1 = F(int((diff * Ix).sum())) * scale
-                    b2 = F(int((diff * Iy).sum())) * scale
+                    b1 = F(window_sum(diff * Ix)) * scale
+                    b2 = F(window_sum(diff * Iy)) * scale
                     dx = (A12 * b2 - A22 * b1) * Dinv
                     dy = (A12 * b1 - A11 * b2) * Dinv
                     nx, ny = nx + dx, ny + dy
@@ -167,6 +188,7 @@ def track(prev_pyr, next_pyr, pts, win, max_count=10, epsilon=0.03, min_eig=1e-4
                     pdx, pdy = dx, dy
                 if l == 0:
                     reason[i] = end
+                note((i, l, end))
             out[i] = (ox, oy)
     return out, status, reason
 

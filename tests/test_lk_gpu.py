@@ -282,6 +282,142 @@ def test_repeat_stream_and_graph_are_bit_identical(lib, device):
             assert np.array_equal(got[1][0].cpu().numpy(), wst)
 
 
+def assert_pyramid_equals(pyr, b, want, what):
+    for l, (img, der) in enumerate(want):
+        got = pyr.level(b, l)
+        assert np.array_equal(got[0], img), (what, l, "image")
+        assert np.array_equal(got[1], der), (what, l, "derivative")
+
+
+@pytest.mark.parametrize("name", list(lk_cases.EDGE_CASES))
+def test_edge_scene_equals_the_oracle_bit_for_bit(name, lib, device):
+    """tests/lk_cases.py EDGE_CASES: windows 3, 5 (lk_track_kernel<1>), 9 (<4>), 17 (<8>), 23 and
+    31 (<16>) on block noise and on the cosine field, 75 x 97 at window 23, window sums beyond
+    2^31 (noise_w23, noise_w31, cosine_w23, cosine_w31, stripes_w31, quilt_w15), two warps, the
+    tight criteria.  Pyramids and derivatives of both frames, next_pts and status."""
+    s = lk_cases.scene(name)
+    want, wst, why, p, q = lk_cases.oracle(name)
+    prev = Pyr(lib, device, s["prev"][None], s["win"], s["max_level"])
+    nxt = Pyr(lib, device, s["next"][None], s["win"], s["max_level"])
+    torch.cuda.synchronize(device)
+    assert prev.levels == nxt.levels == len(p)
+    assert_pyramid_equals(prev, 0, p, name)
+    assert_pyramid_equals(nxt, 0, q, name)
+    n = len(s["pts"])
+    out, st = run_track(lib, device, prev, nxt, s["pts"], [n], n, max_count=s["max_count"],
+                        epsilon=s["epsilon"])
+    bad = np.where((bits(out[0]) != bits(want)).any(1) | (st[0] != wst))[0]
+    assert bad.size == 0, (name, bad[:5], out[0][bad[:5]], want[bad[:5]], why[bad[:5]])
+
+
+@pytest.mark.parametrize("name", ["noise_w31", "cosine_w3"])
+@pytest.mark.parametrize("max_points", [1, 3, 5])
+def test_small_buffers_and_clamped_counts(name, max_points, lib, device):
+    """Buffers of 1, 3 and 5 points: a grid of one partly filled workgroup (3), one full plus
+    one wave (5).  counts equal to max_points, above it, one below it, zero and negative: the
+    rows up to the clamped count equal the oracle's, the rows past it keep their 0xA5 bytes."""
+    s = lk_cases.scene(name)
+    want, wst, _, _, _ = lk_cases.oracle(name)
+    prev = Pyr(lib, device, s["prev"][None], s["win"], s["max_level"])
+    nxt = Pyr(lib, device, s["next"][None], s["win"], s["max_level"], False)
+    pts = s["pts"][20:20 + max_points]      # past the hand-placed points: most of these track
+    for count in (max_points, max_points + 1, 1000, 2 ** 31 - 1, max_points - 1, 0, -1, -2 ** 31):
+        out, st = run_track(lib, device, prev, nxt, pts, [count], max_points)
+        c = min(max(count, 0), max_points)
+        assert np.array_equal(bits(out[0, :c]), bits(want[20:20 + c])), (name, count)
+        assert np.array_equal(st[0, :c], wst[20:20 + c]), (name, count)
+        assert (out[0, c:].view(np.uint32) == UNTOUCHED_F).all() and (st[0, c:] == 0xA5).all()
+
+
+def test_batch_of_a_saturated_and_a_smooth_frame_shares_no_state(lib, device):
+    """Window 31, one keyframe pyramid (block noise) for two next frames in one call: its own
+    rolled copy (window sums up to 4.8e9) and a cosine field.  Each item equals the oracle's
+    result for its pair, in either order of the two, and with per-item counts."""
+    a, b = lk_cases.scene("noise_w31"), lk_cases.scene("cosine_w31")
+    win, ml, pts = a["win"], a["max_level"], a["pts"]
+    want_a, st_a, _, p, _ = lk_cases.oracle("noise_w31")
+    q = lk_oracle.build_pyramid(b["next"], win, ml, with_deriv=False)
+    want_b, st_b, _ = lk_oracle.track(p, q, pts, win)
+    assert st_b.any() and not st_b.all()
+    prev = Pyr(lib, device, a["prev"][None], win, ml)
+    n = len(pts)
+    for order in ((0, 1), (1, 0)):
+        frames = np.stack([(a["next"], b["next"])[i] for i in order])
+        nxt = Pyr(lib, device, frames, win, ml, False)
+        for counts in ((n, n), (n, 7), (5, n)):
+            out, st = run_track(lib, device, prev, nxt, pts, counts, n, shared=True)
+            for item, i in enumerate(order):
+                w, ws = ((want_a, st_a), (want_b, st_b))[i]
+                c = counts[item]
+                assert np.array_equal(bits(out[item, :c]), bits(w[:c])), (order, counts, item)
+                assert np.array_equal(st[item, :c], ws[:c]), (order, counts, item)
+                assert (out[item, c:].view(np.uint32) == UNTOUCHED_F).all()
+                assert (st[item, c:] == 0xA5).all()
+
+
+@pytest.mark.parametrize("name", lk_cases.WARPS)
+def test_warp_scene_is_within_the_model_bar(name, lib, device):
+    """The one comparison that does not pass through the oracle: the GPU against the float64
+    model (tests/lk_model.py) on the rotated and scaled scenes, on the grid points of the host
+    test.  Status equal on every point; where the model ends level 0 by its epsilon rule (all
+    154 points on both warps) the positions agree within the host test's bar, 0.03 px, which
+    was set from the oracle against the model on the CPU (lk_cases.MODEL_BAR; measured there
+    0.0064 and 0.0068 px on these two scenes)."""
+    import lk_model
+    s = lk_cases.scene(name)
+    _, m, pts = lk_cases.model_pair(name)
+    pts = pts.copy()      # the shared one is read-only, which torch.from_numpy warns about
+    prev = Pyr(lib, device, s["prev"][None], s["win"], s["max_level"])
+    nxt = Pyr(lib, device, s["next"][None], s["win"], s["max_level"], False)
+    out, st = run_track(lib, device, prev, nxt, pts, [len(pts)], len(pts))
+    by_eps = m[2] == lk_model.EPS
+    d = np.abs(out[0].astype(np.float64) - m[0]).max(1)
+    print(f"{name}: {int(by_eps.sum())} of {len(pts)} compared, max |GPU - model| "
+          f"{d[by_eps].max():.5f} px")
+    assert np.array_equal(st[0], m[1])
+    assert by_eps.mean() >= lk_cases.COMPARED_SHARE
+    assert d[by_eps].max() <= lk_cases.MODEL_BAR
+
+
+def test_saturated_repeat_stream_and_graph_are_bit_identical(lib, device):
+    """test_repeat_stream_and_graph_are_bit_identical on block noise at window 31 (the
+    16-pixels-per-lane kernel, window sums beyond 2^31)."""
+    s = lk_cases.scene("noise_w31")
+    want, wst, _, _, _ = lk_cases.oracle("noise_w31")
+    win, ml, n = s["win"], s["max_level"], len(s["pts"])
+    prev = Pyr(lib, device, s["prev"][None], win, ml)
+    nxt = Pyr(lib, device, s["next"][None], win, ml, False)
+    first = run_track(lib, device, prev, nxt, s["pts"], [n], n)
+    again = run_track(lib, device, prev, nxt, s["pts"], [n], n)
+    assert np.array_equal(bits(first[0][0]), bits(want)) and np.array_equal(first[1][0], wst)
+    assert np.array_equal(bits(first[0]), bits(again[0])) and np.array_equal(first[1], again[1])
+    side = torch.cuda.Stream(device)
+    with torch.cuda.stream(side):
+        prev_s = Pyr(lib, device, s["prev"][None], win, ml, stream=side.cuda_stream)
+        nxt_s = Pyr(lib, device, s["next"][None], win, ml, False, stream=side.cuda_stream)
+        other = run_track(lib, device, prev_s, nxt_s, s["pts"], [n], n, stream=side.cuda_stream)
+    assert np.array_equal(prev_s.blob.numpy(), prev.blob.numpy())
+    assert np.array_equal(bits(first[0]), bits(other[0])) and np.array_equal(first[1], other[1])
+    img_a = torch.from_numpy(s["prev"]).to(device)
+    img_b = torch.from_numpy(s["next"]).to(device)
+    pts = torch.from_numpy(s["pts"]).to(device)
+    kf = tracker.build_lk_pyramid(img_a, win, ml)
+    counts = torch.full((1,), n, dtype=torch.int32, device=device)
+    eager = tracker.lk_track(kf, tracker.build_lk_pyramid(img_b, win, ml, False), pts, counts)
+    torch.cuda.synchronize(device)
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(graph):
+        cap = tracker.lk_track(kf, tracker.build_lk_pyramid(img_b, win, ml, False), pts, counts)
+    for _ in range(2):
+        cap[0].zero_()
+        cap[1].fill_(7)
+        graph.replay()
+        torch.cuda.synchronize(device)
+        for got in (eager, cap):
+            assert np.array_equal(bits(got[0][0].cpu().numpy()), bits(want))
+            assert np.array_equal(got[1][0].cpu().numpy(), wst)
+
+
 def test_rejected_arguments_write_nothing(lib, device):
     s = lk_cases.scene("one_level")
     prev = Pyr(lib, device, s["prev"][None], s["win"], s["max_level"])

@@ -43,6 +43,130 @@ def test_recorded_set_covers_every_end_reason(gold):
     assert int(gold["one_level_levels"]) == 1 and int(gold["odd_levels"]) == 4
 
 
+@pytest.fixture(scope="module")
+def edges():
+    return np.load(os.path.join(lk_cases.GOLDEN, "lk_edges.npz"))
+
+
+@pytest.mark.parametrize("name", list(lk_cases.EDGE_CASES))
+def test_oracle_reproduces_the_recorded_edge_results(name, edges):
+    s = lk_cases.scene(name)
+    assert lk_cases.scene_sha(s) == str(edges[f"{name}_sha"]), "scene generator changed"
+    nxt, status, why, p, q = lk_cases.oracle(name)
+    assert len(p) == int(edges[f"{name}_levels"])
+    shas = np.array([[lk_cases.sha(i), lk_cases.sha(d)] for pyr in (p, q) for i, d in pyr])
+    assert np.array_equal(shas, edges[f"{name}_pyr_sha"])
+    assert np.array_equal(nxt.view(np.uint32), edges[f"{name}_next_pts"].view(np.uint32))
+    assert np.array_equal(status, edges[f"{name}_status"])
+    assert np.array_equal(why, edges[f"{name}_reason"])
+
+
+@pytest.mark.parametrize("name", list(lk_cases.CASES) + list(lk_cases.EDGE_CASES))
+def test_trace_reproduces_the_recorded_counts_and_changes_nothing(name, edges):
+    """The per-level trace and the largest window sum of every case of both dicts; and track()
+    with a trace gives what it gives without one."""
+    s = lk_cases.scene(name)
+    nxt, status, why, p, q = lk_cases.oracle(name)     # computed with trace and stats
+    trace, max_ix2 = lk_cases.oracle_trace(name)
+    assert np.array_equal(trace, edges[f"{name}_trace"])
+    assert max_ix2 == int(edges[f"{name}_max_ix2"])
+    assert np.array_equal(trace[0, 0], np.bincount(why, minlength=trace.shape[2]))
+    plain = lk_oracle.track(p, q, s["pts"], s["win"], s["max_count"],
+                            s.get("epsilon", lk_cases.EPSILON), lk_cases.MIN_EIG)
+    assert np.array_equal(plain[0].view(np.uint32), nxt.view(np.uint32))
+    assert np.array_equal(plain[1], status) and np.array_equal(plain[2], why)
+
+
+def test_recorded_edge_set_covers_windows_saturation_and_coarse_level_events(edges, gold):
+    """lk_cases.check_coverage, which the generator ran on the live oracle, on the recorded file:
+    both ends of every kernel's window range, window sums beyond 2^31 (2^30 for block noise at
+    window 15) on scenes where points pass the eigenvalue test, the tight criteria, and what
+    happens above level 0 to points that end with status 1."""
+    rec = {}
+    for name in list(lk_cases.CASES) + list(lk_cases.EDGE_CASES):
+        src = gold if name in lk_cases.CASES else edges
+        rec[name] = dict(levels=int(src[f"{name}_levels"]), status=src[f"{name}_status"],
+                         reason=src[f"{name}_reason"], trace=edges[f"{name}_trace"],
+                         max_ix2=int(edges[f"{name}_max_ix2"]))
+    lk_cases.check_coverage(rec)
+
+
+@pytest.mark.parametrize("name", ["base"] + list(lk_cases.SATURATED))
+def test_a_32_bit_window_sum_is_seen_where_the_sums_pass_2_31(name):
+    """A numpy-only power check: the oracle with its five window sums accumulated in int32 with
+    wraparound.  On "base" (largest sum 3.4e7) it is the oracle, bit for bit, so the scenes from
+    before this set cannot see such a width.  It differs where a sum passes 2^31: block noise
+    and stripes at window 31 (4.8e9, 6.2e9; 98 and 96 of 120 points) and the quilt at window 15
+    (3.5e9; 21 points).  Block noise at window 15 reaches 1.6e9, above 2^30 but below 2^31, where
+    an int32 sum is still exact: that scene is identical too, and would show only an accumulator
+    narrower than 32 bits."""
+    s = lk_cases.scene(name)
+    want, wst, _, p, q = lk_cases.oracle(name)
+    _, max_ix2 = lk_cases.oracle_trace(name)
+    out, st, _ = lk_oracle.track(p, q, s["pts"], s["win"], s["max_count"], lk_cases.EPSILON,
+                                 lk_cases.MIN_EIG, window_sum=lk_oracle.wrapped_int32_sum)
+    differ = int(((out.view(np.uint32) != want.view(np.uint32)).any(1) | (st != wst)).sum())
+    print(f"{name}: largest window sum {max_ix2:.3e}, int32 sums differ on {differ} points")
+    if max_ix2 >= 2 ** 31:
+        assert differ >= 10
+    else:
+        assert name in ("base", "noise_w15") and differ == 0
+
+
+@pytest.mark.parametrize("name", list(lk_cases.CASES) + list(lk_cases.EDGE_CASES))
+def test_model_pyramids_equal_the_oracles(name):
+    """pyrDown and Scharr from scipy.ndimage.correlate1d(mode="mirror") against the oracle's
+    index arithmetic: every level and derivative image of both frames, exactly."""
+    import lk_model
+    s = lk_cases.scene(name)
+    _, _, _, p, q = lk_cases.oracle(name)
+    for img, want in ((s["prev"], p), (s["next"], q)):
+        got = lk_model.pyramid(img, s["win"], s["max_level"])
+        assert len(got) == len(want)
+        for (gi, gx, gy), (wi, wd) in zip(got, want):
+            assert gi.dtype == np.uint8 and np.array_equal(gi, wi)
+            assert np.array_equal(gx, wd[..., 0]) and np.array_equal(gy, wd[..., 1])
+
+
+MODEL_BAR = lk_cases.MODEL_BAR   # 0.03 px, from the CPU measurements written beside it
+
+
+@pytest.mark.parametrize("name", lk_cases.MODEL_SCENES)
+def test_oracle_agrees_with_the_float64_model(name):
+    """tests/lk_model.py (true bilinear weights, float64 sums, no fixed point, scipy's
+    interpolation and borders) against the oracle on about 150 grid points more than a window
+    from every border: status equal on every point; on the compared set (both end level 0 by
+    the epsilon rule) positions within MODEL_BAR.  The compared set must be 90% of the points,
+    on every scene but win21, whose shift the pyramid does not carry (see lk_cases.MODEL_ONLY).
+    Measured: compared share 98.7, 92.1, 94.7, 72.7, 96.7, 100, 100 %; maxima 0.00266, 0.01183,
+    0.00292, 0.00568, 0.00210, 0.00643, 0.00683 px; medians 0.0003 to 0.0012 px."""
+    o, m, pts = lk_cases.model_pair(name)
+    cs = lk_cases.compared_set(name)
+    d = np.abs(o[0] - m[0]).max(1)
+    print(f"{name}: {len(pts)} points, {int((o[1] != m[1]).sum())} status differences, compared "
+          f"{int(cs.sum())} ({100 * cs.mean():.1f}%), max {d[cs].max():.5f} px")
+    assert np.array_equal(o[1], m[1])
+    assert name == "win21" or cs.mean() >= lk_cases.COMPARED_SHARE
+    assert d[cs].max() <= MODEL_BAR
+
+
+@pytest.mark.parametrize("name", lk_cases.WARPS)
+def test_warp_error_is_the_models_own(name):
+    """Rotation with scale: no shift to recover, but an analytic displacement per point.  On the
+    interior points (more than 25 px from every border; 117, all kept and all in the compared
+    set) the float64 model's own error against it is 0.557 px (warp_a) and 1.383 px (warp_b):
+    the affine deformation across a 15-px window, not a defect of either side.  The oracle's
+    (0.557, 1.387 px) may exceed the model's by no more than MODEL_BAR."""
+    o, m, pts = lk_cases.model_pair(name)
+    inside = lk_cases.interior(name)
+    truth = pts + lk_cases.warp_truth(name, pts)
+    em, eo = (np.abs(x[0] - truth).max(1)[inside].max() for x in (m, o))
+    print(f"{name}: {int(inside.sum())} interior points, model {em:.4f} px, oracle {eo:.4f} px")
+    assert inside.sum() >= 100 and o[1][inside].all() and lk_cases.compared_set(name)[inside].all()
+    assert em <= 2.0          # a lost point is off by its displacement, 3 to 9 px on these
+    assert eo <= em + MODEL_BAR
+
+
 # h, w, shift, win, seed: no noise, no flat patch; the last needs all three levels for its shift
 KNOWN = [(120, 160, (3.3, -2.6), 15, 21), (120, 160, (9.4, 6.2), 15, 22),
          (200, 240, (14.0, -11.0), 21, 23)]
