@@ -703,7 +703,11 @@ int onepose_nn_similarity_top2(const void* desc0, int64_t desc0_bstride, const v
  * What the reference pins: the cost function only.  residual[n] = f (R(aa) X + t).xy / (.).z +
  * (cx, cy) - (u, v) with X = points[ptIdx[n]], (aa, t) = cam_pose[camIdx[n]], (u, v, f, cx, cy) =
  * features[n]; the rotation takes the reference's two branches (theta^2 > 0: Rodrigues, else
- * X + aa x X), and at theta^2 == 0 the Jacobian is that branch's derivative, -[X]x.  DeepLM's
+ * X + aa x X), and at theta^2 == 0 the Jacobian is that branch's derivative, -[X]x.  For
+ * 0 < theta^2 < 1e-4 the Jacobian's coefficients (1 - cos) / theta^2, (cos - sin / theta) /
+ * theta^2 and (sin / theta - 2 (1 - cos) / theta^2) / theta^2 come from their series (the closed
+ * forms cancel to nothing there and overflow at a subnormal theta^2); the residual does not
+ * change.  DeepLM's
  * source is not in the reference tree and cv2 is not a dependency here, so the solver below is
  * this project's own (parity with DeepLM's iterates and with cv2's SVD is NOT verified); it is
  * restated in numpy float64 in tests/ba_oracle.py, which the GPU tests compare against.

@@ -39,6 +39,7 @@ constexpr int kBaMagic = 0x42413031;      // "BA01"
 constexpr int kBaHeader = 8;              // int32 words: magic, N, C, P, A, Pa, 0, 0
 constexpr int kBaCholThreads = 256;
 constexpr int kBaSchurThreads = 128;
+constexpr double kBaSeriesTh2 = 1e-4;     // theta^2 below which the Jacobian's b, ca, ab are series
 enum { BA_OK = 0, BA_FAILED = 1, BA_BAD_INDEX = 2 };
 
 struct BaState {
@@ -118,7 +119,8 @@ void ba_carve(BaArgs& a, void* ws, size_t* bytes) {
 // SnavelyReprojectionErrorV2 for one observation: cam = (angle-axis, t), X, ft = (u, v, f, cx,
 // cy).  Jc (2 x 6, row-major) and Jp (2 x 3) may be null.  The rotation follows
 // AngleAxisRotatePoint operation by operation; the Jacobian is the derivative of that same
-// expression, R X = c X + a (w x X) + b w (w . X) with a = sin / theta, b = (1 - cos) / theta^2,
+// expression, R X = c X + a (w x X) + b w (w . X) with a = sin / theta, b = (1 - cos) / theta^2
+// (its coefficients by series below theta^2 = 1e-4; the residual path is untouched),
 // and at theta^2 == 0 the derivative of the first-order branch X + w x X, i.e. -[X]x and I + [w]x.
 __device__ __forceinline__ void ba_observe(const double* cam, const double* X, const double* ft,
                                            double* r, double* Jc, double* Jp) {
@@ -127,7 +129,7 @@ __device__ __forceinline__ void ba_observe(const double* cam, const double* X, c
   const double th2 = w0 * w0 + w1 * w1 + w2 * w2;
   const double wx0 = w1 * x2 - w2 * x1, wx1 = w2 * x0 - w0 * x2, wx2 = w0 * x1 - w1 * x0;
   const double wd = w0 * x0 + w1 * x1 + w2 * x2;
-  double p0, p1, p2, c = 1.0, a = 1.0, b = 0.0, th = 0.0;
+  double p0, p1, p2, c = 1.0, a = 1.0, th = 0.0;
   if (th2 > 0.0) {
     th = sqrt(th2);
     c = cos(th);
@@ -138,7 +140,6 @@ __device__ __forceinline__ void ba_observe(const double* cam, const double* X, c
     p1 = x1 * c + (k2 * x0 - k0 * x2) * s + k1 * tmp;
     p2 = x2 * c + (k0 * x1 - k1 * x0) * s + k2 * tmp;
     a = s / th;
-    b = (1.0 - c) / th2;
   } else {
     p0 = x0 + wx0;
     p1 = x1 + wx1;
@@ -160,7 +161,19 @@ __device__ __forceinline__ void ba_observe(const double* cam, const double* X, c
   const double Xx[3][3] = {{0.0, -x2, x1}, {x2, 0.0, -x0}, {-x1, x0, 0.0}};
   const double Wx[3][3] = {{0.0, -w2, w1}, {w2, 0.0, -w0}, {-w1, w0, 0.0}};
   if (th2 > 0.0) {
-    const double ca = (c - a) / th2, ab = (a - 2.0 * b) / th2;
+    // b = (1 - cos) / theta^2, ca = (cos - a) / theta^2, ab = (a - 2 b) / theta^2: below
+    // kBaSeriesTh2 from their series (error < 1e-16 there).  The closed forms cancel to nothing
+    // under theta = 1e-8, and a subnormal theta^2 overflows the quotient into a NaN Jacobian.
+    double b, ca, ab;
+    if (th2 >= kBaSeriesTh2) {
+      b = (1.0 - c) / th2;
+      ca = (c - a) / th2;
+      ab = (a - 2.0 * b) / th2;
+    } else {
+      b = 0.5 + th2 * (-1.0 / 24.0 + th2 * (1.0 / 720.0));
+      ca = -1.0 / 3.0 + th2 * (1.0 / 30.0 + th2 * (-1.0 / 840.0));
+      ab = -1.0 / 12.0 + th2 * (1.0 / 180.0 + th2 * (-1.0 / 6720.0));
+    }
 #pragma unroll
     for (int i = 0; i < 3; ++i)
 #pragma unroll

@@ -14,6 +14,7 @@ INFO_HEAD, INFO_ROW, INFO_ITERS = 8, 6, 16
 INFO_DOUBLES = INFO_HEAD + INFO_ROW * INFO_ITERS
 ST_OK, ST_FAILED, ST_BAD_INDEX = 0, 1, 2
 MIN_RHO = 1e-3
+SERIES_TH2 = 1e-4   # theta^2 below which the Jacobian takes b, ca, ab from their series
 
 
 def _skew(v):
@@ -43,9 +44,16 @@ def linearize(points, cams, feats, pt_idx, cam_idx, jac=True):
         return r
     N = len(X)
     a = np.where(pos, s / th, 1.0)
-    b = np.where(pos, (1.0 - c) / np.where(pos, th2, 1.0), 0.0)
-    ca = np.where(pos, (c - a) / np.where(pos, th2, 1.0), 0.0)
-    ab = np.where(pos, (a - 2.0 * b) / np.where(pos, th2, 1.0), 0.0)
+    # the Jacobian's coefficients: closed forms from SERIES_TH2 up, their series below it (there
+    # 1 - cos, cos - a and a - 2 b cancel to nothing, and a subnormal theta^2 overflows the
+    # quotient: the closed form gives NaN at |aa| = 1e-160)
+    big = th2 >= SERIES_TH2
+    den = np.where(big, th2, 1.0)
+    b = np.where(big, (1.0 - c) / den, 0.5 + th2 * (-1.0 / 24.0 + th2 * (1.0 / 720.0)))
+    ca = np.where(big, (c - a) / den, -1.0 / 3.0 + th2 * (1.0 / 30.0 + th2 * (-1.0 / 840.0)))
+    ab = np.where(big, (a - 2.0 * b) / den,
+                  -1.0 / 12.0 + th2 * (1.0 / 180.0 + th2 * (-1.0 / 6720.0)))
+    b, ca, ab = np.where(pos, b, 0.0), np.where(pos, ca, 0.0), np.where(pos, ab, 0.0)
     cc = np.where(pos, c, 1.0)
     eye = np.eye(3)[None]
     wd = (w * X).sum(1)

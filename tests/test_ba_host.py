@@ -318,3 +318,110 @@ def test_cam_param_round_trip_and_project():
         r = O.linearize(X, bal[None, :6], feats, np.arange(5), np.zeros(5, int), jac=False)
         # (near pi the matrix-to-vector direction keeps about 1e-10 of the axis)
         assert np.abs(r).max() < (1e-6 if ang > 3 else 1e-9)
+
+
+# ---- the oracle against the many-digit model, the dense step and its own edge fixtures ----------
+def _golden(name):
+    return np.load(os.path.join(ba_cases.GOLDEN, name))
+
+
+def test_oracle_matches_the_model_at_the_edges():
+    """The grid is rebuilt from its recorded seed and digest, and ba_oracle.linearize is held to
+    the bars the GPU kernel is held to (16 x its own recorded deviation from the mpmath model per
+    angle, floors 1e-14 of max|J| and 64 ulps of the residual's largest intermediate)."""
+    g = _golden("ba_edges.npz")
+    prob, ang = ba_cases.edge_grid(int(g["seed"]))
+    assert ba_cases.problem_sha(prob) == str(g["sha"]), "synthetic inputs changed"
+    assert len(ang) == 608 and g["bar_Jc"].shape == g["bar_Jp"].shape == g["bar_r"].shape == (19,)
+    assert (g["bar_Jc"] >= 1e-14).all() and (g["bar_Jp"] >= 1e-14).all()
+    # the float64 formula is nowhere further than 1e-6 max|J| from the model (the series took
+    # the place of the closed forms below theta^2 = 1e-4; without it theta = 1e-160 gives NaN)
+    assert max(g["dev_Jc"].max(), g["dev_Jp"].max()) < 1e-6
+    r, Jc, Jp = O.linearize(prob["points"], prob["cam_pose"], prob["features"], prob["ptIdx"],
+                            prob["camIdx"])
+    assert np.isfinite(Jc).all() and np.isfinite(Jp).all()
+    ratios = ba_cases.edge_ratios(r, Jc, Jp, g, ang)
+    assert (ratios <= 1.0).all(), ratios.max(0)
+    th2 = (prob["cam_pose"][:, :3] ** 2).sum(1)
+    assert (th2 == 0).sum() == 32 and ((th2 > 0) & (th2 < 1e-300)).sum() == 32
+    z = r[:, 0] * 0 + np.array([ba_cases.EDGE_GEOMETRY[i // 2 % 4][2] for i in range(608)])
+    assert (z < 0).sum() == 152 and np.isclose(np.abs(z).min(), 0.02)
+
+
+@pytest.mark.parametrize("name", list(ba_cases.STEP_CASES))
+def test_oracle_first_step_is_the_damped_gauss_newton_step(name):
+    g = _golden("ba_dense.npz")
+    prob = ba_cases.STEP_CASES[name]()
+    assert ba_cases.problem_sha(prob) == str(g[f"{name}_sha"]), "synthetic inputs changed"
+    pts, cams, info = O.solve(prob["points"], prob["cam_pose"], prob["features"], prob["ptIdx"],
+                              prob["camIdx"], 1, 1, ba_cases.STEP_RADIUS)
+    tol, row = g[f"{name}_tol"], O.rows(info)[0]
+    assert info[1] == 1 and info[2] == 1
+    assert np.abs(ba_cases.step_of(prob, pts, cams) - g[f"{name}_delta"]).max() <= tol[0]
+    assert abs(row[2] / float(g[f"{name}_md"]) - 1) <= tol[1]
+    assert abs(row[1] / float(g[f"{name}_cand"]) - 1) <= tol[2]
+    assert 6 * len(np.unique(prob["camIdx"])) + 3 * len(np.unique(prob["ptIdx"])) == len(
+        g[f"{name}_delta"]) <= (207 if name == "lanes" else 120)
+
+
+@pytest.mark.parametrize("name", list(ba_cases.MIN_CASES))
+def test_oracle_reaches_the_minimum(name):
+    g = _golden("ba_dense.npz")
+    prob = ba_cases.MIN_CASES[name][0](int(g[f"{name}_seed"]))
+    assert ba_cases.problem_sha(prob) == str(g[f"{name}_sha"]), "synthetic inputs changed"
+    _, _, info = O.solve(prob["points"], prob["cam_pose"], prob["features"], prob["ptIdx"],
+                         prob["camIdx"], 16, 16, 1e4)
+    opt = float(g[f"{name}_opt"])
+    assert (info[4] - opt) / opt <= float(g[f"{name}_gap_bar"]) and info[1] == 16
+    assert float(g[f"{name}_gap_bar"]) == 1e-9 and len(prob["ptIdx"]) <= 500
+
+
+@pytest.mark.parametrize("name", list(ba_cases.SOLVE_EDGE_CASES))
+def test_oracle_reproduces_its_edge_fixture(name):
+    g = _golden("ba_solve_edges.npz")
+    prob, radius, iters, succ, exp = ba_cases.load_solve_edge(name, g)
+    with np.errstate(all="ignore"):
+        pts, cams, info = O.solve(prob["points"], prob["cam_pose"], prob["features"],
+                                  prob["ptIdx"], prob["camIdx"], iters, succ, radius)
+    assert np.array_equal(pts, exp["points"]) and np.array_equal(cams, exp["cam_pose"])
+    assert np.array_equal(info, exp["info"], equal_nan=True)
+    rw, sig = O.rows(info), O.significant(info)
+    assert exp["tol"].shape == (5,) and (exp["tol"] >= 1e-12).all() and exp["tol"][0] <= 16e-6
+    assert (np.abs(rw[sig, 3] - O.MIN_RHO) >= 0.05).all()
+    if name == "chol_fail":   # the header: a failed Cholesky gives NaN, NaN, NaN and moves nothing
+        assert info[0] == O.ST_OK and info[1] == 5 and info[2] == 0
+        assert np.isnan(rw[:, 1:4]).all() and (rw[:, 5] == 0).all() and (rw[:, 0] == info[3]).all()
+        assert rw[:, 4].tolist() == [1e4, 5e3, 1250.0, 156.25, 9.765625]
+        assert info[5] == 0.30517578125 and np.isfinite(info[3])
+        assert np.array_equal(pts, prob["points"]) and np.array_equal(cams, prob["cam_pose"])
+        assert (prob["features"][:, 2] == 1e154).all()
+    if name == "reject_run":
+        assert rw[:, 5].astype(int).tolist()[:5] == [1, 0, 0, 0, 1] and sig.all() and info[1] == 8
+    if name == "radius_cap_1e16":
+        assert rw[0, 5] == 1 and sig[0] and (rw[1:, 4] == 1e16).all()
+    if name == "lane_counts":
+        assert np.bincount(prob["camIdx"]).tolist() == [1, 63, 64, 65, 128, 129]
+        assert len(np.unique(prob["ptIdx"])) == 140
+    if name == "behind":
+        n0 = 17
+        cam = prob["cam_pose"][prob["camIdx"][n0]]
+        z = (synthetic._rodrigues_np(cam[:3]) @ prob["points"][prob["ptIdx"][n0]] + cam[3:])[2]
+        assert abs(z + 0.3) < 1e-12
+
+
+def test_triangulation_edge_fixture():
+    """The inputs are rebuilt and their digests compared; numpy.linalg.eigh(A^T A) stays within
+    the recorded bar (it defined a sixteenth of it) and gives the reference's keep mask."""
+    g = _golden("triangulate_edges.npz")
+    for name in ba_cases.TRI_EDGE_CASES:
+        P1, P2, p1, p2 = ba_cases.tri_edge_inputs(name)
+        assert ba_cases.sha(P1, P2, p1, p2) == str(g[f"{name}_sha"]), name
+        thr, zmax = float(g[f"{name}_rep_thr"]), float(g[f"{name}_z_max"])
+        X, e1, e2, z, keep = O.triangulate_filter(P1, P2, p1, p2, thr, zmax, method="eig")
+        dev = max(np.abs(X - g[f"{name}_points"]).max(), np.abs(e1 - g[f"{name}_err1"]).max(),
+                  np.abs(e2 - g[f"{name}_err2"]).max())
+        assert dev <= float(g[f"{name}_tol"]) and np.array_equal(keep, g[f"{name}_keep"]), name
+        assert len(p1) == 130 and 0 < keep.sum() < 130
+        ref = g[f"{name}_points"][:, 2]
+        for v, t in ((g[f"{name}_err1"], thr), (g[f"{name}_err2"], thr), (ref, zmax)):
+            assert np.abs(v / t - 1).min() >= 1e-6 and (v > t).any()

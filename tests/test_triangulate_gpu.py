@@ -9,6 +9,7 @@ import pytest
 import torch
 
 import ba_cases
+import ba_oracle as O
 from ba_cases import Guarded
 from onepose_amd import _lib, tracker
 
@@ -97,3 +98,58 @@ def test_python_layer_inverts_tcw(tri, device):
     rm = np.unique(np.concatenate([np.where(r1 > 20)[0], np.where(r2 > 20)[0],
                                    np.where(pts[:, 2] > 0.15)[0]]))
     assert np.array_equal(np.where(~keep)[0], rm)
+
+
+# ---- the tracker's own geometry, against a 50-digit eigenvector ---------------------------------
+@pytest.fixture(scope="module")
+def tri_edges():
+    return np.load(os.path.join(ba_cases.GOLDEN, "triangulate_edges.npz"))
+
+
+@pytest.mark.parametrize("name", list(ba_cases.TRI_EDGE_CASES))
+def test_triangulate_matches_the_model_at_short_baselines(name, lib, tri_edges, device):
+    """130 pairs (three workgroups) at baselines of 0.1 .. 2 degrees, with and without noise, and
+    at f = 3000, against mpmath.eigsy at 50 digits (tests/golden/make_golden_tri_edges.py).  The
+    bar is 16 x what numpy.linalg.eigh(A^T A) in float64 deviates from that, floor 1e-12; the
+    keep masks are equal (every decision is >= 1e-6 from the case's thresholds)."""
+    P1, P2, p1, p2 = ba_cases.tri_edge_inputs(name)
+    assert ba_cases.sha(P1, P2, p1, p2) == str(tri_edges[f"{name}_sha"])
+    thr, zmax = float(tri_edges[f"{name}_rep_thr"]), float(tri_edges[f"{name}_z_max"])
+    X, e1, e2, z, keep = run(lib, device, P1, P2, p1, p2, thr, zmax)
+    tol = float(tri_edges[f"{name}_tol"])
+    dev = max(np.abs(X - tri_edges[f"{name}_points"]).max(),
+              np.abs(e1 - tri_edges[f"{name}_err1"]).max(),
+              np.abs(e2 - tri_edges[f"{name}_err2"]).max())
+    print(f"{name}: deviation {dev:.2e} (tol {tol:.1e}, ratio {dev / tol:.3f}), kept "
+          f"{int(keep.sum())}")
+    assert np.array_equal(keep, tri_edges[f"{name}_keep"])
+    assert dev <= tol
+    assert (e1 > thr).any() and (e2 > thr).any() and (z > zmax).any() and keep.any()
+
+
+def _tri_property_inputs(tri_edges):
+    for name in ba_cases.TRI_EDGE_CASES:
+        yield (name, ba_cases.tri_edge_inputs(name), float(tri_edges[f"{name}_rep_thr"]),
+               float(tri_edges[f"{name}_z_max"]))
+    for name, inputs in ba_cases.tri_degenerate_inputs().items():
+        yield name, inputs, 20.0, 1e300
+
+
+def test_triangulate_properties(lib, tri_edges, device):
+    """Over every case and two degenerate inputs (identical views; a pixel pair at both epipoles,
+    A^T A exactly singular twice): a kept pair has a finite X whose reprojection errors,
+    recomputed on the host from the returned X, are within the threshold (+ 1e-9 px) and whose z
+    is; z is X[:, 2]; two runs are bit-equal; guards are intact (run() asserts them).  No claim
+    about which degenerate pairs are kept."""
+    for name, (P1, P2, p1, p2), thr, zmax in _tri_property_inputs(tri_edges):
+        X, e1, e2, z, keep = run(lib, device, P1, P2, p1, p2, thr, zmax)
+        again = run(lib, device, P1, P2, p1, p2, thr, zmax)
+        for a, b in zip((X, e1, e2, z, keep), again):
+            assert np.array_equal(a, b, equal_nan=True), name
+        assert np.array_equal(z, X[:, 2], equal_nan=True), name
+        assert np.isfinite(X[keep]).all(), name
+        with np.errstate(all="ignore"):
+            h1, h2 = O.reproject(P1, X[keep], p1[keep]), O.reproject(P2, X[keep], p2[keep])
+        assert (h1 <= thr + 1e-9).all() and (h2 <= thr + 1e-9).all(), name
+        assert (z[keep] <= zmax).all(), name
+        print(f"{name}: kept {int(keep.sum())} of {len(keep)}")
