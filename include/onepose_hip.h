@@ -883,6 +883,101 @@ int onepose_lk_track(const void* prev_pyr, int64_t prev_pyr_bstride, const void*
                      void* stream);
 
 /* ------------------------------------------------------------------------------------ *
+ * Object builder  --  SfM filter, merge and descriptor lifting
+ *   The reference's postprocess stage (run.py:196-249): filter_points.filter_3d and
+ *   filter_points.merge (src/sfm/postprocess/filter_points.py:8-117) and
+ *   feature_process.get_kpt_ann's gather and averaging (feature_process.py:59-188, 297-305),
+ *   plus data_utils.build_features3d_leaves' gather (src/utils/data_utils.py:163-205).
+ * Versioned on its own: onepose_objbuild_version() returns 1; onepose_abi_version() was not
+ * bumped.  Not here: score means (numpy sums a [k, 1] column pairwise; they stay on the host),
+ * the leaf permutation (numpy's RNG; the host supplies the indices), anno_2d.json.
+ *
+ * Every floating-point step below is one IEEE operation, rounded to nearest even, in the order
+ * written; a*b + c is never fused; sqrt and / are correctly rounded.  No floating-point atomics
+ * and a fixed order in every sum: results are bit-identical from run to run.  Merge and lifting
+ * reproduce the reference bit for bit; the box test's dot product is this project's own order
+ * (torch.matmul's differs in the last bits), so it is pinned to the reference only for points
+ * that keep a margin from every face.
+ *
+ * All pointers are device pointers.  No entry point allocates, frees or synchronises.  Checks
+ * on the host (null pointers, sizes, flags) return ONEPOSE_ERR_INVALID before anything is
+ * launched, and nothing is written.  What only the device can see is reported in a device
+ * `info` array, and the call then writes nothing but what is said below.
+ *
+ * onepose_filter_points: stable compaction.  xyz [n, 3] fp64 in ascending point-id order,
+ *   track_len [n] int32 (NULL: no track filter), corners [8, 3] fp64 (NULL: no box filter),
+ *   1 <= n <= 2^24.  Point i is kept iff track_len[i] >= min_track and it passes the box test:
+ *     c = float32(corners), p = float32(xyz[i]);  q = p - c[4];
+ *     for v in (c[5] - c[4], c[0] - c[4], c[7] - c[4]):
+ *       m = (q0 v0 + q1 v1) + q2 v2;  vv = (v0 v0 + v1 v1) + v2 v2;  pass iff 0 < m and m < vv
+ *   all in fp32, both comparisons strict, so a point on a face and a NaN coordinate fail.
+ *   xyz_out [n, 3] fp32 = float32(xyz[i]) and index_out [n] int32 = i for the kept points, in
+ *   input order; count [1] int32.  Rows from count on are not written.  One workgroup walks the
+ *   points 1024 at a time.
+ *
+ * onepose_radius_neighbours: xyz [n, 3] of xyz_dtype (ONEPOSE_OBJ_F32 / _F64), 1 <= n <= 65536,
+ *   thr positive and finite.  i is a neighbour of j iff i == j or sqrt(s) < thr with
+ *     dx = double(x_i) - double(x_j), dy, dz alike;  s = (dx dx + dy dy) + dz dz
+ *   (scipy's pdist on the widened values; squareform's diagonal is 0, hence i == j).  Output: a
+ *   CSR, row_start [n + 1] int32 and cols [cols_capacity] int32, row j holding its neighbours
+ *   ascending.  Three launches: a count per row (one wave per row), a scan, and the same walk
+ *   again placing each lane by a ballot prefix; the n x n matrix is never written.
+ *   info [2] int64: [0] the total number of pairs, [1] 0 written, 1 the total exceeds
+ *   cols_capacity, 2 it exceeds 2^31 - 1.  With [1] != 0 nothing is written to cols and
+ *   row_start is not to be used; cols_capacity == 0 (cols may be NULL) is the size query.
+ *
+ * onepose_merge_greedy: the greedy pass over that CSR, on the same xyz.  For j = 0 .. n - 1: if
+ *   any neighbour of j is already recorded, skip j; otherwise the neighbours of j become the next
+ *   cluster and are recorded.  A skipped point that no later cluster picks up is dropped (for a
+ *   chain a-b-c seeded at a the cluster is {a, b} and c is lost), as in the reference.
+ *   cluster_of [n] int32 (-1: dropped);  member_start [n + 1] int32 and members [n] int32, a CSR
+ *   of each cluster's points ascending;  mean [n, 3] fp64, of which the first info[0] rows are
+ *   written:  s = x[m0]; s = s + x[m1]; ... in the member order and in the dtype of xyz, then
+ *   s / count in that dtype, then widened.  info [2] int32: [0] the cluster count, [1] 0, or 1
+ *   when row_start / cols is not a CSR over n points (an entry outside [0, n), an empty row, more
+ *   members than points); the other outputs are then unspecified, and nothing was read or
+ *   written through the bad entry.  The pass is sequential in j by definition: one wave, at most
+ *   n row visits (worst case: no row is its own only neighbour); a run of consecutive rows that
+ *   are each their own only neighbour becomes a run of clusters in one step.
+ *
+ * onepose_lift_descriptors: the 3D descriptor lifting.  bank: bank_numel fp32, holding image
+ *   block b as [dim, block_cols[b]] (as the extractor emits it) from element block_offset[b]
+ *   (int64); observation o is column obs_feat[o] of block obs_block[o] (both int32), in collect
+ *   order; seg_len [n3] int32 is the reference's idxs (observations per 3D point).
+ *   1 <= dim <= 1024, 1 <= n3 <= n_obs <= 2^28, 1 <= n_blocks <= 2^20.
+ *     collected [dim, n_obs] fp64 = double(bank value);
+ *     mean64 [dim, n3] fp64:  s = first; s = s + next; ... over the segment in observation order,
+ *       then s / double(count);   mean32 [dim, n3] fp32 = float32(mean64);
+ *     seg_start [n3 + 1] int32: the segments' first observations.
+ *   info [2] int32: [0] 0, or 1 a segment of length < 1, 2 the lengths do not add up to n_obs,
+ *   3 a block outside the bank, 4 an observation outside its block; [1] the smallest offending
+ *   index.  With [0] != 0 none of collected, mean64, mean32 is written (a block that no
+ *   observation uses is fine).  One thread per (3D point, channel).
+ *
+ * onepose_gather_leaves: out [dim, n_cols] fp32, column i = float32(collected[:, cols[i]]);
+ *   cols [n_cols] int64, where cols[i] == n_obs is the dustbin, a column of ones; any other
+ *   value outside [0, n_obs) gives a column of NaN and nothing is read through it.
+ * ------------------------------------------------------------------------------------ */
+#define ONEPOSE_OBJ_F32 0
+#define ONEPOSE_OBJ_F64 1
+int onepose_objbuild_version(void);
+int onepose_filter_points(const double* xyz, const int* track_len, int n, int min_track,
+                          const double* corners, float* xyz_out, int* index_out, int* count,
+                          void* stream);
+int onepose_radius_neighbours(const void* xyz, int xyz_dtype, int n, double thr, int* row_start,
+                              int* cols, int64_t cols_capacity, int64_t* info, void* stream);
+int onepose_merge_greedy(const void* xyz, int xyz_dtype, int n, const int* row_start,
+                         const int* cols, int* cluster_of, int* member_start, int* members,
+                         double* mean, int* info, void* stream);
+int onepose_lift_descriptors(const float* bank, int64_t bank_numel, const int64_t* block_offset,
+                             const int* block_cols, int n_blocks, const int* obs_block,
+                             const int* obs_feat, int n_obs, const int* seg_len, int n3, int dim,
+                             int* seg_start, double* collected, double* mean64, float* mean32,
+                             int* info, void* stream);
+int onepose_gather_leaves(const double* collected, int n_obs, int dim, const int64_t* cols,
+                          int n_cols, float* out, void* stream);
+
+/* ------------------------------------------------------------------------------------ *
  * Measurement hook (bench.py's roofline). While enabled, every launch whose kernel kind
  * is in `kind_mask` (bit k = kind k, names from onepose_profile_kind_name) is bracketed by
  * two HIP events recorded on the launch's own stream.  Host-side state, not for use during

@@ -201,6 +201,18 @@ PROTOTYPES = {
     "onepose_lk_track": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_int,
                                  c_int, c_int, c_int, c_int, c_int, c_int, c_float, c_float,
                                  c_void_p, c_void_p, c_void_p]),
+    "onepose_objbuild_version": (c_int, []),
+    "onepose_filter_points": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p,
+                                      c_void_p, c_void_p, c_void_p]),
+    "onepose_radius_neighbours": (c_int, [c_void_p, c_int, c_int, c_double, c_void_p, c_void_p,
+                                          c_int64, c_void_p, c_void_p]),
+    "onepose_merge_greedy": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p,
+                                     c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "onepose_lift_descriptors": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_int, c_void_p,
+                                         c_void_p, c_int, c_void_p, c_int, c_int, c_void_p,
+                                         c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "onepose_gather_leaves": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_void_p,
+                                      c_void_p]),
     "onepose_profile_begin": (c_int, [ctypes.c_uint64, c_int]),
     "onepose_profile_begin_device": (c_int, [ctypes.c_uint64]),
     "onepose_profile_end_device": (c_int, [c_void_p, c_void_p, c_int]),

@@ -157,6 +157,20 @@ class OnePoseObject:
         kp3, avg, leaves = data_utils.load_object_annotations(anno_dir, num_leaf)
         return cls(kp3, avg, leaves, device)
 
+    @classmethod
+    def from_sfm_model(cls, model_dir: str, features, img_lists, box, num_leaf: int = 8,
+                       max_num_kp3d: int = 2500, dist_threshold: float = 1e-3, device="cuda"):
+        """Builds the object from its SfM model (``points3D.bin`` / ``images.bin`` in
+        ``model_dir``) and the per-image features on the device (``onepose_amd.object_builder``:
+        filter, merge, descriptor lifting, leaf gather) without touching the disk.  Seeded like
+        ``from_anno_dir`` (``seed_reference_stream``), its tensors equal those read back from the
+        files ``object_builder.build_annotations`` writes."""
+        from . import object_builder
+        kp3, avg, leaves = object_builder.object_tensors(
+            model_dir, features, img_lists, box, num_leaf=num_leaf, max_num_kp3d=max_num_kp3d,
+            dist_threshold=dist_threshold, device=device)
+        return cls(kp3, avg, leaves, device)
+
 
 # ------------------------------------------------------------------ per frame
 def load_image(path: str, grayscale: bool = True):
