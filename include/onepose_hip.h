@@ -949,6 +949,10 @@ int onepose_lk_track(const void* prev_pyr, int64_t prev_pyr_bstride, const void*
  *     mean64 [dim, n3] fp64:  s = first; s = s + next; ... over the segment in observation order,
  *       then s / double(count);   mean32 [dim, n3] fp32 = float32(mean64);
  *     seg_start [n3 + 1] int32: the segments' first observations.
+ *   The sum is sequential at every dim.  That is the reference's mean_descriptors bit for bit
+ *   for dim >= 2 (np.mean(axis=0) on a [k, dim] block adds row by row).  At dim == 1 the block is
+ *   one contiguous run and numpy sums it pairwise, so the reference -- and this package's
+ *   device=None path, which takes the reference's route -- may differ from the device there.
  *   info [2] int32: [0] 0, or 1 a segment of length < 1, 2 the lengths do not add up to n_obs,
  *   3 a block outside the bank, 4 an observation outside its block; [1] the smallest offending
  *   index.  With [0] != 0 none of collected, mean64, mean32 is written (a block that no

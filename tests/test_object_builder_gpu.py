@@ -1,9 +1,12 @@
 """The object builder's kernels (csrc/object_build.hip) on the GPU: every output bit-equal to the
 numpy oracle (tests/object_builder_oracle.py) and, at the fixture size, to what the reference
 itself produced (tests/golden/object_builder.npz).  Every buffer is followed by guard words that
-must survive, and every case runs twice and must give equal bits."""
+must survive, and every case runs twice and must give equal bits.  The second half is the
+adversarial pass: order-sensitive sums, clusters longer than a wave, every 1024-chunk edge,
+hand-built neighbour lists, special values and the size limits (DESIGN.md 8i has the table)."""
 import functools
 import os
+import time
 
 import numpy as np
 import pytest
@@ -62,6 +65,7 @@ def run_filter(dev, xyz, tl, min_track, corners):
     m = int(cnt.numpy()[0])
     i = idx.numpy()
     assert (i[m:] == UNTOUCHED).all()        # rows from count on are not written
+    assert (out.numpy((n, 3))[m:].view(np.int32) == UNTOUCHED).all()
     return out.numpy((n, 3))[:m].copy(), i[:m].copy()
 
 
@@ -146,19 +150,7 @@ def run_merge(dev, x, rs, cols):
 def cloud(n, dtype):
     """n points with natural near pairs (a dense corner) and, from 64 on, planted duplicates,
     clusters and both chains; with its oracle results."""
-    rs = np.random.RandomState(900 + n)
-    items = []
-    if n >= 64:
-        items = C.planted(rs, lambda: rs.uniform(0.2, 1.0, 3))
-    elif n == 2:
-        items = [("dup", [np.full(3, 0.5), np.array([0.5, 0.5003, 0.5])])]
-    left = n - sum(len(p) for _, p in items)
-    dense = left // 8 if n >= 257 else 0
-    side = 0.0125 * (dense / 512.0) ** (1 / 3) if dense else 0.0
-    items += [("s", [rs.uniform(0.0, side, 3)]) for _ in range(dense)]
-    items += [("s", [rs.uniform(0.2, 1.0, 3)]) for _ in range(left - dense)]
-    x = np.concatenate([np.stack(items[k][1]) for k in rs.permutation(len(items))]).astype(dtype)
-    assert x.shape == (n, 3)
+    x = C.cloud_points(n, dtype)
     rs_o, cols_o = O.radius_neighbours(x, C.THR)
     return x, rs_o, cols_o, O.merge_greedy(x, rs_o, cols_o)
 
@@ -261,14 +253,7 @@ def test_merge_refuses_a_broken_csr(device):
 # ------------------------------------------------------------------ lifting
 @functools.lru_cache(maxsize=None)
 def lift_case(dim):
-    rs = np.random.RandomState(70 + dim)
-    ncols = np.array([300, 257, 64, 411, 90], dtype=np.int32)     # block 2 is used by nobody
-    off = np.concatenate([[0], np.cumsum(ncols[:-1].astype(np.int64) * dim)]).astype(np.int64)
-    bank = rs.randn(int((ncols.astype(np.int64) * dim).sum())).astype(np.float32)
-    seg = np.array([1, 2, 63, 64, 65, 519, 1, 7, 8, 9, 130], dtype=np.int32)
-    S = int(seg.sum())
-    blk = rs.choice([0, 1, 3, 4], size=S).astype(np.int32)
-    feat = (rs.randint(0, 1 << 30, size=S) % ncols[blk]).astype(np.int32)
+    bank, off, ncols, blk, feat, seg = C.lift_inputs_old(dim)
     return bank, off, ncols, blk, feat, seg, O.lift(bank, off, ncols, blk, feat, seg, dim)
 
 
@@ -391,3 +376,214 @@ def test_build_annotations_writes_the_reference_files(device, tmp_path):
     for name in ("keypoints3d", "descriptors3d", "leaves"):
         ta, tb = getattr(a, name), getattr(b, name)
         assert tb.device.type == "cuda" and same(tb.cpu().numpy(), ta.cpu().numpy()), name
+
+
+# ================================================================== the second pass
+# Inputs from tests/object_builder_cases.py; the reference's bits for them from
+# tests/golden/object_builder_edges.npz (make_golden_object_builder_edges.py);
+# tests/test_object_builder_model_host.py shows which wrong kernel each input separates.
+@functools.lru_cache(maxsize=None)
+def wide_lift(n3, dim):
+    args = C.lift_inputs(n3, dim)
+    return args, O.lift(*args, dim)
+
+
+@pytest.mark.parametrize("n3,dim", C.LIFT_GPU)
+def test_lifting_on_a_wide_bank_past_the_first_chunk(device, n3, dim):
+    """Sums whose float64 value depends on their order, segment starts carried over 1024-chunks
+    of points, blocks and observations."""
+    args, want = wide_lift(n3, dim)
+    info, ss, col, m64, m32 = twice(lambda: run_lift(device, *args, dim))
+    assert info.tolist() == [0, 0]
+    for a, b in zip((ss, col, m64, m32), want):
+        assert same(a, b)
+    key = f"lift_{n3}_{dim}_ref_sha"
+    assert (C.sha(m64) == str(golden("object_builder_edges")[key])) == (dim >= 2)
+
+
+def test_lifting_refuses_past_the_first_chunk(device):
+    dim = 3
+    (bank, off, ncols, blk, feat, seg), _ = wide_lift(2500, dim)
+    S = len(blk)
+    assert S > 16000
+
+    def changed(a, **at):
+        a = a.copy()
+        for k, v in at.items():
+            a[int(k[1:])] = v
+        return a
+    cases = (
+        ((off, blk, feat, changed(seg, _2047=0, _2048=seg[2047] + seg[2048])), [1, 2047]),
+        ((off, blk, feat, changed(seg, _1500=0, _40=-3)), [1, 40]),
+        ((off, blk, feat, changed(seg, _2499=seg[2499] - 1)), [2, S - 1]),
+        ((off, blk, feat, changed(seg, _0=seg[0] + 1)), [2, S + 1]),
+        ((changed(off, _1499=off[1499] + 1), blk, feat, seg), [3, 1499]),
+        ((off, blk, changed(feat, _16000=ncols[blk[16000]], _1030=ncols[blk[1030]]), seg), [4, 1030]),
+    )
+    assert cases[0][0][3].sum() == S
+    for (o, b, f, s), want in cases:
+        info, ss, col, m64, m32 = twice(lambda: run_lift(device, bank, o, ncols, b, f, s, dim))
+        assert info.tolist() == want
+        for a in (col, m64, m32):                    # nothing is written
+            assert (a.view(np.uint8) == 0xA5).all()
+
+
+def test_lifting_through_the_public_function_at_scale(device):
+    (bank, off, ncols, blk, feat, seg), want = wide_lift(2500, 256)
+    desc = C.lift_blocks(bank, off, ncols, 256)
+    got = twice(lambda: [t.cpu().numpy() for t in ob.lift_descriptors(desc, blk, feat, seg,
+                                                                      device=device)])
+    host = ob.lift_descriptors(desc, blk, feat, seg, device=None)
+    for a, b, c in zip(got, host, want[1:]):
+        assert same(a, b) and same(a, c)
+    # dim 1: the device is sequential (the oracle); the host path follows the reference's
+    # pairwise np.mean and differs on this bank (include/onepose_hip.h)
+    (bank, off, ncols, blk, feat, seg), want = wide_lift(1025, 1)
+    desc = C.lift_blocks(bank, off, ncols, 1)
+    got = twice(lambda: [t.cpu().numpy() for t in ob.lift_descriptors(desc, blk, feat, seg,
+                                                                      device=device)])
+    for a, c in zip(got, want[1:]):
+        assert same(a, c)
+    assert not same(ob.lift_descriptors(desc, blk, feat, seg, device=None)[1], got[1])
+
+
+@pytest.mark.parametrize("n", C.FILTER_N)
+@pytest.mark.parametrize("box", [True, False])
+def test_filter_at_the_chunk_edges(device, n, box):
+    xyz, _, corners = filter_inputs(n, 40 + n)
+    corners = corners if box else None
+    for pattern in C.FILTER_PATTERNS:
+        tl = C.filter_pattern(n, pattern)
+        got = twice(lambda: run_filter(device, xyz, tl, 3, corners))
+        want = O.filter_points(xyz, tl, 3, corners)
+        assert same(got[0], want[0]) and same(got[1], want[1]), pattern
+        if not box:
+            assert np.array_equal(got[1], np.nonzero(tl >= 3)[0]), pattern
+        if pattern == "none":
+            assert len(got[1]) == 0
+    if box:
+        assert 0 < len(O.filter_points(xyz, None, 0, corners)[1]) < n
+
+
+@pytest.mark.parametrize("dtype", [np.float32, np.float64])
+@pytest.mark.parametrize("name", C.CSR_CASES)
+def test_merge_structure_on_hand_built_lists(device, name, dtype):
+    x, rs, cols = C.csr_case(name, dtype)
+    want = O.merge_greedy(x, rs, cols)
+    got = twice(lambda: run_merge(device, x, rs, cols))     # run_merge: info == [m, 0]
+    for a, b in zip(got, want):
+        assert same(a, b)
+    cof, ms, mem, mean = got
+    if name == "all_alone":
+        assert np.array_equal(cof, np.arange(C.CSR_N)) and np.array_equal(mem, np.arange(C.CSR_N))
+    if name == "group_multi":
+        assert len(ms) - 1 == 64 + 32 + 2 and (cof >= 0).all()
+    if name == "seen_at_100":
+        assert cof[1] == -1 and len(ms) - 1 == C.CSR_N - 1
+    if name == "row_order":
+        row = cols[:129].tolist()
+        assert len(ms) - 1 == 2 and mem[:129].tolist() == row != sorted(row)
+        if dtype == np.float32:      # the row's order, not ascending order
+            assert not same(mean[0], C.mean_in_order(x, sorted(row)))
+    if name == "asym_ab":
+        assert cof[40] == cof[20] and len(ms) - 1 == C.CSR_N - 1
+    if name == "asym_ba":
+        assert cof[40] == -1 and cof[20] == 20
+    if name == "not_self":
+        assert cof[30] == -1 and cof[31] == 30 and cof[127] == -1
+
+
+@pytest.mark.parametrize("name", list(C.LONG_MERGE_CASES))
+def test_long_clusters_against_the_reference(device, name):
+    g = golden("object_builder_edges")
+    xyz, ids, thr, groups = C.long_merge_case(name)
+    assert C.sha(xyz, ids) == str(g[f"merge_{name}_sha"])
+    pts, ret = ob.merge(xyz, ids, thr, device=device)
+    pts2, ret2 = ob.merge(xyz, ids, thr, device=device)
+    lens, flat = C.flatten_clusters(ret)
+    assert same(pts, g[f"merge_{name}_points"]) and same(pts, pts2)
+    assert same(lens, g[f"merge_{name}_lens"]) and same(flat, g[f"merge_{name}_ids"])
+    assert same(C.flatten_clusters(ret2)[1], flat)
+    rs_o, cols_o = O.radius_neighbours(xyz, thr)
+    cof, ms, mem, _ = check_neighbours_and_merge(device, xyz, thr, rs_o, cols_o,
+                                                 O.merge_greedy(xyz, rs_o, cols_o))
+    assert sorted(np.diff(ms))[-7:] == [63, 64, 65, 65, 128, 129, 200]
+    assert cof[groups["skip"][0][65]] == -1
+
+
+@pytest.mark.parametrize("name", list(C.threshold_cases()))
+def test_neighbours_across_the_bound_limits(device, name):
+    x, thr = C.threshold_cases()[name]
+    rs_o, cols_o = O.radius_neighbours(x, thr)
+    total = int(rs_o[-1])
+    assert total >= len(x) + 30                      # the planted groups survive the scaling
+    rs, cols, info = twice(lambda: run_neighbours(device, x, thr, total))
+    assert info.tolist() == [total, 0]
+    assert np.array_equal(rs, rs_o) and same(cols[:total], cols_o)
+
+
+@pytest.mark.parametrize("dtype", [np.float32, np.float64])
+def test_neighbours_of_special_values(device, dtype):
+    cases = [C.special_cloud(dtype)]
+    if dtype == np.float64:
+        cases += [C.underflow_case(), (C.sq_separator(), C.THR32)]
+    for x, thr in cases:
+        rs_o, cols_o = O.radius_neighbours(x, thr)
+        total = int(rs_o[-1])
+        rs, cols, info = twice(lambda: run_neighbours(device, x, thr, total))
+        assert info.tolist() == [total, 0]
+        assert np.array_equal(rs, rs_o) and same(cols[:total], cols_o)
+
+
+def test_pair_count_refusal(device):
+    t0 = time.perf_counter()
+    for n, status in ((46340, 1), (46341, 2)):
+        x = np.tile(np.array([[0.1, 0.2, 0.3]], dtype=np.float32), (n, 1))
+        rs, cols, info = twice(lambda: run_neighbours(device, x, C.THR, 0))
+        assert info.tolist() == [n * n, status]
+        assert np.array_equal(rs, np.minimum(np.arange(n + 1, dtype=np.int64) * n, 2**31 - 1))
+        assert (cols == UNTOUCHED).all()
+    assert n * n > 2**31 - 1
+    rs, cols, info = twice(lambda: run_neighbours(device, x, C.THR, 1024))
+    assert info.tolist() == [n * n, 2]
+    assert len(cols) == 1024 and (cols == UNTOUCHED).all()       # nothing is written through the list
+    with pytest.raises(_lib.OnePoseError, match=str(n * n)):
+        ob.radius_neighbours_device(torch.from_numpy(x).to(device), C.THR)
+    print(f"pair-count refusal: {time.perf_counter() - t0:.2f} s")
+
+
+def test_the_largest_cloud(device):
+    """n = 65536: the last word of the recorded bitmap, against a pruned host search that
+    tests/test_object_builder_model_host.py holds to the oracle."""
+    t0 = time.perf_counter()
+    x, pairs, triple = C.big_cloud()
+    rs_o, cols_o = C.pruned_neighbours(x, C.THR)
+    merge_o = O.merge_greedy(x, rs_o, cols_o)
+    t1 = time.perf_counter()
+    cof, ms, mem, _ = check_neighbours_and_merge(device, x, C.THR, rs_o, cols_o, merge_o)
+    t2 = time.perf_counter()
+    c = cof[65535]
+    assert c >= 0 and mem[ms[c]:ms[c + 1]].tolist() == list(triple)
+    assert cof[0] == cof[40000] == 0
+    assert rs_o[-1] >= len(x) + 2 * len(pairs) + 6
+    print(f"n = 65536: host {t1 - t0:.2f} s, device calls and comparison {t2 - t1:.2f} s")
+
+
+def test_chain_at_scale_equals_the_host_path(device):
+    pts, imgs, corners, desc = C.chain_model()
+
+    def chain(dev):
+        x, ids = ob.filter_3d(pts, C.CHAIN_TKL, corners, device=dev)
+        mp, mi = ob.merge(x, ids, C.THR, device=dev)
+        oi, of, idxs = ob.collect_observations(imgs, C.CHAIN_IMAGES, mi)
+        lifted = ob.lift_descriptors(desc, oi, of, idxs, device=dev)
+        lens, flat = C.flatten_clusters(mi)
+        return [x.numpy(), ids, mp, lens, flat, oi, of, idxs] + [
+            t.cpu().numpy() if isinstance(t, torch.Tensor) else t for t in lifted]
+    got = twice(lambda: chain(device))
+    want = chain(None)
+    assert len(got) == len(want) == 11
+    for a, b in zip(got, want):
+        assert same(a, b)
+    n3 = len(got[7])
+    assert 1024 < n3 < len(got[1]) < len(pts["ids"]) and got[3].max() >= 2
