@@ -982,6 +982,91 @@ int onepose_gather_leaves(const double* collected, int n_obs, int dim, const int
                           int n_cols, float* out, void* stream);
 
 /* ------------------------------------------------------------------------------------ *
+ * Sparse reconstruction  --  feature tracks and multi-view triangulation
+ *   The part of the reference's sfm_core (run.py:140-193) that follows matching: the tracks that
+ *   COLMAP forms from the imported matches, and the points its point_triangulator computes from
+ *   them with the poses held fixed (src/sfm/triangulation.py:122-148).
+ * Versioned on its own: onepose_sfm_version() returns 1; onepose_abi_version() was not bumped.
+ *
+ * No COLMAP source or binary is at hand, so the triangulator below is this project's own:
+ * parity with COLMAP's point_triangulator is NOT verified and is not claimed.  The defaults the
+ * Python layer passes (max_reproj 4 px, min_angle 1.5 degrees) follow COLMAP's documented mapper
+ * defaults in name only.  Not here: geometric verification, RANSAC over the observations, bundle
+ * adjustment, point colours.  tests/sfm_oracle.py restates both entry points in plain loops.
+ *
+ * All pointers are device pointers.  No entry point allocates, frees or synchronises; both can
+ * be captured in a graph, and the launch sequence of a call depends on its host arguments only.
+ * No floating-point atomics, and every sum over a track's observations is taken in ascending
+ * position: results are bit-identical from run to run.  a*b + c is never fused.  Host checks
+ * (null pointers, sizes, NaN thresholds) return ONEPOSE_ERR_INVALID before anything is launched.
+ *
+ * onepose_track_components: connected components of the graph whose nodes are the features
+ *   (global feature id = the image's feature offset + the keypoint index) and whose edges
+ *   [n_edges, 2] int32 are the matches.  parent [n_nodes] int32: on return the label of a node is
+ *   the smallest id of its component.  That result is unique, so the integer atomicMin below
+ *   leaves nothing to scheduling.  1 <= n_nodes <= 2^30, 0 <= n_edges <= 2^30 (edges may be NULL
+ *   at 0), 0 <= rounds <= 64.  Launches: one that sets parent[i] = i when init != 0 and zeroes
+ *   status; then per round
+ *     compress: every node walks to its root (parent[r] == r) and stores it.  parent[x] <= x
+ *       holds throughout and a parent only ever decreases, so a concurrent reader sees a node of
+ *       the same component; a root is never written, so every walk ends at a true root;
+ *     hook: per edge with roots ru != rv, atomicMin(&parent[max(ru, rv)], min(ru, rv)).  The
+ *       launch returns at once when the previous round joined nothing;
+ *   then a final compress and a check.  status [4] int32: [0] the edges whose ends still carry
+ *   different labels (0: converged), [1] the rounds that joined something, [2] the edges with an
+ *   end outside [0, n_nodes): they are ignored and nothing is read through them, [3] internal.
+ *   With init == 0 the call continues from parent as an earlier call left it, so a caller loops
+ *   while status[0] != 0 and correctness never rests on `rounds`; a parent value outside [0, x]
+ *   (an array no first call wrote) ends a walk, and nothing is read through it.
+ *
+ * onepose_tracks_triangulate: Rt [n_images, 3, 4] (x_cam = R X + t) and K4 [n_images, 4] = (fx,
+ *   fy, cx, cy), fp64; the tracks as a CSR, track_start [n_tracks + 1] int32 over obs_image
+ *   [n_obs] int32 (an index into Rt / K4) and obs_xy [n_obs, 2] fp64 pixels (the Python layer
+ *   adds 0.5 to the extractor's keypoints, as the reference's import_features does).
+ *   1 <= n_tracks <= 2^24, 1 <= n_obs <= 2^28.  Two launches: the check, then one wave per track.
+ *   The check (one workgroup) runs before anything is read through the CSR: status [2] int32,
+ *   [0] = 0, or 1 when track_start is not 0 = s[0] <= s[1] <= ... <= s[n_tracks] = n_obs, or 2
+ *   when an image id lies outside [0, n_images); [1] the smallest offending index.  With
+ *   status[0] != 0 no output is written.
+ *   Per track, with S = all its observations (positions 0 .. len - 1):
+ *   1 DLT: an observation contributes the rows xn Rt[2] - Rt[0] and yn Rt[2] - Rt[1], xn = (u -
+ *     cx) / fx, yn = (v - cy) / fy.  M = A^T A, each entry summed over S as m = m + (a_i a_j +
+ *     b_i b_j); the eigenvector of its smallest eigenvalue by cyclic Jacobi, exactly as
+ *     onepose_triangulate takes it; X = h[0:3] / h[3].
+ *   2 Score: p = Rt X, residual = (fx p0 / p2 + cx - u, fy p1 / p2 + cy - v), e = its norm; an
+ *     observation is an inlier iff p2 > 0 and e <= max_reproj.  If any observation of S fails,
+ *     the worst leaves S (the largest e, p2 <= 0 counting as +inf, ties to the lowest position)
+ *     and step 1 runs again; fewer than 2 left: reason 1.
+ *   3 Duplicates: of several observations of S in one image the one with the smallest e stays
+ *     (ties to the lowest position); fewer than 2 left: reason 1.
+ *   4 Refine: at most 5 Gauss-Newton steps on cost = sum over S of |residual|^2.  H = sum J^T J,
+ *     g = sum J^T r with J = d residual / dX; H = L L^T, H d = -g; X + d is taken iff its cost is
+ *     strictly smaller.  The first rejected step or pivot that is not > 0 ends the refinement.
+ *   5 Final check: e at the refined X; observations that now fail leave S (no new solve); fewer
+ *     than 2 left: reason 1.  With unit rays from X to the camera centres -R^T t, the largest
+ *     angle between two rays of S is acos(clamp(smallest dot product)); below min_angle_deg:
+ *     reason 2.
+ *   A track of length < 2 or > onepose_sfm_max_track() (256): reason 3, nothing read.  A
+ *   non-finite X after a solve, or a NaN error or dot product: reason 4.
+ *   Outputs: reason [n_tracks] int32 (0: kept); xyz [n_tracks, 3]; err [n_tracks], the mean of e
+ *   over the final S, summed in ascending position; n_kept [n_tracks] int32 = |S|; obs_keep
+ *   [n_obs] uint8, 1 for the final S.  A track with reason != 0 gets NaN, NaN, 0 and zeros.
+ *   Mapping: lanes over the observations for the per-observation terms, which are staged in LDS
+ *   (20 KB per wave; no per-thread array is indexed at run time); ten lanes each sum one unique
+ *   entry of A^T A (then of H, g and the cost) serially; every lane then holds the sums and runs
+ *   the 4 x 4 Jacobi and the 3 x 3 Cholesky itself.
+ * ------------------------------------------------------------------------------------ */
+int onepose_sfm_version(void);
+int onepose_sfm_max_track(void);
+int onepose_track_components(const int* edges, int n_edges, int n_nodes, int rounds, int init,
+                             int* parent, int* status, void* stream);
+int onepose_tracks_triangulate(const double* Rt, const double* K4, int n_images,
+                               const int* track_start, const int* obs_image, const double* obs_xy,
+                               int n_tracks, int n_obs, double max_reproj, double min_angle_deg,
+                               double* xyz, double* err, int* reason, int* n_kept,
+                               uint8_t* obs_keep, int* status, void* stream);
+
+/* ------------------------------------------------------------------------------------ *
  * Measurement hook (bench.py's roofline). While enabled, every launch whose kernel kind
  * is in `kind_mask` (bit k = kind k, names from onepose_profile_kind_name) is bracketed by
  * two HIP events recorded on the launch's own stream.  Host-side state, not for use during

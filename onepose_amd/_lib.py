@@ -213,6 +213,13 @@ PROTOTYPES = {
                                          c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "onepose_gather_leaves": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_void_p,
                                       c_void_p]),
+    "onepose_sfm_version": (c_int, []),
+    "onepose_sfm_max_track": (c_int, []),
+    "onepose_track_components": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p,
+                                         c_void_p]),
+    "onepose_tracks_triangulate": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p,
+                                           c_int, c_int, c_double, c_double, c_void_p, c_void_p,
+                                           c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "onepose_profile_begin": (c_int, [ctypes.c_uint64, c_int]),
     "onepose_profile_begin_device": (c_int, [ctypes.c_uint64]),
     "onepose_profile_end_device": (c_int, [c_void_p, c_void_p, c_int]),
