@@ -124,8 +124,10 @@ enum GemmTile {
   TILE_32x128 = 1,  // qkv (QKV: one head's [k_h | v_h] or two q heads per tile)
   TILE_64x32K2 = 2, // mlp2 fp32 (RESID + NORM): 64 x 32 outputs, K split over two wave pairs
                     //   (N = 256 gives 2x the 64x64 tile count: 640 tiles at config 2)
-  TILE_64x128 = 3,  // qkv fp32 at large batches: 2 accumulators per wave, 64-row KV chunks
-  TILE_128x128 = 4, // qkv fp32 at larger batches: 4 accumulators per wave, 128-row KV chunks
+  TILE_64x128 = 3,  // bf16 / split-mode qkv, bf16 mlp1 and its acc0: 2 accumulators per wave,
+                    //   64-row KV chunks (its fp32 qkv kernel: replaced by TILE_128x128W8 in
+                    //   round 5, removed with the variant table)
+  TILE_128x128 = 4, // qkv fp32 at the largest batches: 4 accumulators per wave, 128-row KV chunks
   TILE_32x64W2 = 6,  // mlp2 in the split mode: 32 x 64 outputs on 2 waves (N = 256: 640 tiles
                      //   at config 2, where 64 x 64 gives 320 for 256 CUs)
   TILE_128x64W8 = 5, // score: 128 x 64 outputs on 8 waves of 32 x 32 (K = 256 is short: half
@@ -133,39 +135,94 @@ enum GemmTile {
   TILE_32x256W8 = 8, // final projection + L2 normalisation (EPI_BIAS_L2): whole rows on 8 waves
                      //   of 32 x 32 (two per SIMD), 64-deep stages
   // (9: a 256 x 128 eight-wave bf16 MLP conv 1 tile, measured slower; removed, tag r05-lab)
-  TILE_128x128W8 = 10, // split-mode MLP conv 1 (STATS + HEADZ, DMA 2): 128 x 128 on 8 waves of
-                       //   32 x 64, standing in for 64 x 64 tiles the same way (acc0 included)
+  TILE_128x128W8 = 10, // split-mode MLP conv 1 (STATS + HEADZ, DMA 2) and fp32 qkv at large
+                       //   batches: 128 x 128 on 8 waves of 32 x 64, standing in for 64 x 64
+                       //   (qkv: 64 x 128) tiles the same way (acc0 included)
 };
-// Output tile shape of each configuration, usable in constant expressions (the workspace
-// plan sizes per-tile partials and counters from these; tile_dims in gemm.hip agrees).
-constexpr int gemm_tile_bm(int t) {
-  return (t == TILE_32x128 || t == TILE_32x64W2 || t == TILE_32x256W8) ? 32
-         : (t == TILE_128x128 || t == TILE_128x64W8) ? 128
-         : t == TILE_128x128W8                       ? 128
-                                                     : 64;
+// The one table of tile shapes, usable in constant expressions: BM x BN outputs, the K loop's
+// stage depth, and the rows per EPI_STATS partial (and per acc0 tile) -- the tile's own, or its
+// stand-in tile's.  The workspace plan sizes per-tile partials and counters from these, and each
+// Tile<> in gemm.hip asserts its parameters against its row.  bm = 0: no such configuration.
+struct GemmTileShape {
+  int bm, bn, bks, stat_rows;
+};
+constexpr GemmTileShape gemm_tile_shape(int t) {
+  switch (t) {
+    case TILE_64x64: return {64, 64, 32, 64};
+    case TILE_32x128: return {32, 128, 32, 32};
+    case TILE_64x32K2: return {64, 32, 64, 64};
+    case TILE_64x128: return {64, 128, 32, 64};
+    case TILE_128x128: return {128, 128, 32, 128};
+    case TILE_128x64W8: return {128, 64, 32, 128};
+    case TILE_32x64W2: return {32, 64, 32, 32};
+    case TILE_32x256W8: return {32, 256, 64, 32};
+    case TILE_128x128W8: return {128, 128, 32, 64};
+    default: return {0, 0, 0, 0};
+  }
 }
-// rows per EPI_STATS partial (and per acc0 tile): the tile's, or its stand-in tile's
-constexpr int gemm_tile_stat_rows(int t) {
-  return t == TILE_128x128W8 ? 64 : gemm_tile_bm(t);
-}
-constexpr int gemm_tile_bn(int t) {
-  return (t == TILE_32x128 || t == TILE_64x128 || t == TILE_128x128 || t == TILE_128x128W8)
-             ? 128
-         : t == TILE_64x32K2                                        ? 32
-         : t == TILE_32x256W8                                       ? 256
-                                                                    : 64;
-}
+constexpr int gemm_tile_bm(int t) { return gemm_tile_shape(t).bm; }
+constexpr int gemm_tile_bn(int t) { return gemm_tile_shape(t).bn; }
+constexpr int gemm_tile_bks(int t) { return gemm_tile_shape(t).bks; }
+constexpr int gemm_tile_stat_rows(int t) { return gemm_tile_shape(t).stat_rows; }
 // (STATS + HEADZ also compile for 64x32 / 2 waves and for 64x64 / 8 waves with K split in
 // two and 64-deep stages, one head per stage; both measured slower than 64x64 for mlp1 in the
 // two-stream frame: DESIGN.md section 3.)
 
-// Supported (epilogue, prologue, tile) combinations: QKV/32x128, STATS+HEADZ/64x64,
-// RESID+NORM/64x64 and /64x32K2 (fp32), SCORE/64x64, BIAS/64x64.  K must be a multiple of twice the tile's stage
-// depth (32 * KS).
-// pm = PM_BF16: operands rounded to bf16 as the stage is stored, v_mfma_f32_32x32x16_bf16 with
-// fp32 accumulation (QKV, STATS+HEADZ, RESID+NORM 64x64 only: the attention-layer GEMMs).
-// pm = PM_SPLIT3: every operand split exactly into three bf16 pieces, six bf16 MFMAs per
-// 16-deep group (fp32-accurate; all 64x64 and 32x128 combinations).
+// The kernels the library has: one row per gemm_kernel instantiation, and no instantiation
+// without a row.  wpl: W from bf16 planes (GemmProb::Wp); dma: 0 the register-staged K loop, 1 W
+// planes by global_load_lds, 2 A planes by global_load_lds as well (gemm.hip).  Which call reaches
+// each row, under what condition, and which rows were removed: DESIGN.md section 3a.
+struct GemmVariant {
+  int epi, pro, tile, pm;
+  bool wpl;
+  int dma;
+};
+constexpr GemmVariant kGemmVariants[] = {
+    // fp32 (also the final projection, the score GEMM and SuperGlue in every attention mode)
+    {EPI_QKV, PRO_PLAIN, TILE_32x128, PM_F32, false, 0},
+    {EPI_QKV, PRO_PLAIN, TILE_128x128W8, PM_F32, false, 0},
+    {EPI_QKV, PRO_PLAIN, TILE_128x128, PM_F32, false, 0},
+    {EPI_STATS, PRO_HEADZ, TILE_64x64, PM_F32, false, 0},
+    {EPI_RESID, PRO_NORM_RELU, TILE_64x64, PM_F32, false, 0},
+    {EPI_RESID, PRO_NORM_RELU, TILE_64x32K2, PM_F32, false, 0},
+    {EPI_SCORE, PRO_PLAIN, TILE_128x64W8, PM_F32, false, 0},
+    {EPI_BIAS, PRO_PLAIN, TILE_64x64, PM_F32, false, 0},
+    {EPI_BIAS_L2, PRO_PLAIN, TILE_32x256W8, PM_F32, false, 0},
+    {EPI_ACC, PRO_PLAIN, TILE_64x64, PM_F32, false, 0},
+    // bf16 attention layers: W from the packed bf16 planes (weights rounded on the host, Mf by
+    // the KV fold), A from the producers' activation planes (DMA 2) or rounded as the stage is
+    // stored
+    {EPI_QKV, PRO_PLAIN, TILE_64x128, PM_BF16, true, 2},
+    {EPI_STATS, PRO_HEADZ, TILE_64x128, PM_BF16, true, 2},
+    {EPI_RESID, PRO_NORM_RELU, TILE_64x64, PM_BF16, true, 0},
+    {EPI_ACC, PRO_PLAIN, TILE_64x128, PM_BF16, true, 1},
+    // split-mode attention layers: the same with three planes per operand
+    {EPI_QKV, PRO_PLAIN, TILE_64x128, PM_SPLIT3, true, 2},
+    {EPI_STATS, PRO_HEADZ, TILE_128x128W8, PM_SPLIT3, true, 2},
+    {EPI_RESID, PRO_NORM_RELU, TILE_32x64W2, PM_SPLIT3, true, 1},
+    {EPI_RESID, PRO_NORM_RELU, TILE_64x64, PM_SPLIT3, true, 1},
+    {EPI_ACC, PRO_PLAIN, TILE_64x64, PM_SPLIT3, true, 1},
+    // final projection and score GEMM in the split mode (activations as W: VALU split)
+    {EPI_SCORE, PRO_PLAIN, TILE_64x64, PM_SPLIT3, false, 0},
+    {EPI_BIAS, PRO_PLAIN, TILE_64x64, PM_SPLIT3, false, 0},
+};
+constexpr bool gemm_same_variant(const GemmVariant& a, const GemmVariant& b) {
+  return a.epi == b.epi && a.pro == b.pro && a.tile == b.tile && a.pm == b.pm && a.wpl == b.wpl &&
+         a.dma == b.dma;
+}
+constexpr bool gemm_has_variant(const GemmVariant& want) {
+  for (const GemmVariant& v : kGemmVariants)
+    if (gemm_same_variant(v, want)) return true;
+  return false;
+}
+constexpr bool gemm_has_variant(int epi, int pro, int tile, int pm, bool wpl, int dma) {
+  return gemm_has_variant(GemmVariant{epi, pro, tile, pm, wpl, dma});
+}
+
+// K must be a multiple of twice the tile's stage depth.  pm (below): PM_BF16 rounds operands to
+// bf16 (v_mfma_f32_32x32x16_bf16, fp32 accumulation); PM_SPLIT3 splits every operand exactly into
+// three bf16 pieces, six bf16 MFMAs per 16-deep group (fp32-accurate).  A combination without a
+// row in kGemmVariants is ONEPOSE_ERR_INVALID.
 int gemm_launch(int epi, int pro, int tile, GemmArgs& args, hipStream_t stream, int kind,
                 int pm = PM_F32);
 // Rows per M-tile of a configuration (the chunk size of the STATS / KVPART partials).

@@ -21,6 +21,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <type_traits>
+#include <utility>
 
 // Pins the pipeline's phase order (the compiler's own schedule measured within +-2%,
 // DESIGN.md §3d).
@@ -386,8 +387,11 @@ __device__ __forceinline__ void gemm_body(const GemmArgs& args, StampTick& tk, S
     }
   }
 
-  // RESID with at most two residual float4 per thread (fp32 MLP conv 2's 64 x 32 tile): the
-  // row-store pass's R loads ahead of the K loop too (the same rows and columns it reads there)
+  // RESID with at most four residual float4 per thread (RPER <= 4): the row-store pass's R loads
+  // ahead of the K loop too (the same rows and columns it reads there).  That is every RESID
+  // tile of the variant table: 64 x 32 K2 (two per thread), 64 x 64 in all three operand modes
+  // and the split mode's 32 x 64 W2 (four each); a 64 x 128 tile (eight) would load them in the
+  // row-store pass.
   constexpr int RPER = BM * (BN / 4) / T::NT;
   constexpr bool kRPre = EPI == EPI_RESID && RPER <= 4 && (BM * (BN / 4)) % T::NT == 0;
   float4 r_pre[kRPre ? RPER : 1];
@@ -563,27 +567,29 @@ __device__ __forceinline__ void gemm_body(const GemmArgs& args, StampTick& tk, S
     for (int j = 0; j < FN; ++j)
 #pragma unroll
       for (int i = 0; i < 16; ++i) acc[j][i] = a0p[j * 1024 + i * 64];
-  } else if (acc0 != nullptr) {
+  } else if constexpr (T::NSUB > 1) {
     // acc0 as the 64 x SUBN four-wave tile stored it (2 x 2 waves of 32 x SUBN / 2, FNp
     // accumulators each): this wave's 32 rows are sub-tile wm / 2's wave row wm % 2; its
     // 32-column block cb (global column n0 + 32 cb) is that tile's column tile (n0 + 32 cb) /
     // SUBN, wave column cbp / FNp, accumulator cbp % FNp for cbp = its block within that tile
     // (sub-tiles past M hold nothing and are never stored)
     constexpr int SN = T::SUBN, FNP = SN / 64;
-    static_assert(T::NSUB == 1 || (T::SUB == 64 && T::KS == 1 && (SN == 64 || SN == 128) &&
-                                   (BN % SN == 0 || SN % BN == 0)),
+    static_assert(T::SUB == 64 && T::KS == 1 && (SN == 64 || SN == 128) &&
+                      (BN % SN == 0 || SN % BN == 0),
                   "acc0 of 64-row sub-tiles");
-    const int st = mt * T::NSUB + wm / 2;
-    const int ntp = c.N / SN;   // the stand-in grid's column tiles
-    if (st * 64 < c.M) {
-      const float* a0b = acc0 + b * F(acc0_bs) + lane;
+    if (acc0 != nullptr) {
+      const int st = mt * T::NSUB + wm / 2;
+      const int ntp = c.N / SN;   // the stand-in grid's column tiles
+      if (st * 64 < c.M) {
+        const float* a0b = acc0 + b * F(acc0_bs) + lane;
 #pragma unroll
-      for (int j = 0; j < FN; ++j) {
-        const int gc = n0 + (wn * FN + j) * 32, cbp = (gc % SN) / 32;
-        const float* a0p = a0b + ((int64_t)(st * ntp + gc / SN) * 4 + (wm % 2) * 2 + cbp / FNP) *
-                                     FNP * 1024 + (cbp % FNP) * 1024;
+        for (int j = 0; j < FN; ++j) {
+          const int gc = n0 + (wn * FN + j) * 32, cbp = (gc % SN) / 32;
+          const float* a0p = a0b + ((int64_t)(st * ntp + gc / SN) * 4 + (wm % 2) * 2 + cbp / FNP) *
+                                       FNP * 1024 + (cbp % FNP) * 1024;
 #pragma unroll
-        for (int i = 0; i < 16; ++i) acc[j][i] = a0p[i * 64];
+          for (int i = 0; i < 16; ++i) acc[j][i] = a0p[i * 64];
+        }
       }
     }
   }
@@ -1326,16 +1332,30 @@ void gemm_kernel(GemmArgs args) {
   stamp_end(args.stamp, tk, &sl);
 }
 
-using T64x64 = Tile<64, 64, 1, 4, 32>;
-using T32x128 = Tile<32, 128, 1, 4, 32>;
-using T64x32K2 = Tile<64, 32, 2, 4, 64>;
-using T64x128 = Tile<64, 128, 1, 4, 32>;
-using T128x128 = Tile<128, 128, 1, 4, 32>;
-using T128x64W8 = Tile<128, 64, 1, 8, 32>;
-using T32x64W2 = Tile<32, 64, 1, 2, 32>;
-using T32x256W8 = Tile<32, 256, 1, 8, 64, 1>;
-using T128x128W8S = Tile<128, 128, 1, 8, 32, 2, 64, 64>;   // split MLP conv 1 for the 64 x 64 tile
-
+// Each configuration's Tile<>, checked against its row of gemm.h's shape table where it is
+// defined; TileOf maps the GemmTile value to it for the variant dispatch.
+template <int TILE>
+struct TileOf;
+#define ONEPOSE_TILE(NAME, ID, ...)                                                        \
+  using NAME = Tile<__VA_ARGS__>;                                                          \
+  static_assert(NAME::BM == gemm_tile_bm(ID) && NAME::BN == gemm_tile_bn(ID) &&            \
+                    NAME::BKS == gemm_tile_bks(ID) && NAME::SUB == gemm_tile_stat_rows(ID), \
+                #NAME " differs from gemm.h's tile table");                                \
+  template <>                                                                              \
+  struct TileOf<ID> {                                                                      \
+    using type = NAME;                                                                     \
+  };
+ONEPOSE_TILE(T64x64, TILE_64x64, 64, 64, 1, 4, 32)
+ONEPOSE_TILE(T32x128, TILE_32x128, 32, 128, 1, 4, 32)
+ONEPOSE_TILE(T64x32K2, TILE_64x32K2, 64, 32, 2, 4, 64)
+ONEPOSE_TILE(T64x128, TILE_64x128, 64, 128, 1, 4, 32)
+ONEPOSE_TILE(T128x128, TILE_128x128, 128, 128, 1, 4, 32)
+ONEPOSE_TILE(T128x64W8, TILE_128x64W8, 128, 64, 1, 8, 32)
+ONEPOSE_TILE(T32x64W2, TILE_32x64W2, 32, 64, 1, 2, 32)
+ONEPOSE_TILE(T32x256W8, TILE_32x256W8, 32, 256, 1, 8, 64, 1)
+// (stands in for 64 x 64 tiles: split MLP conv 1, fp32 QKV)
+ONEPOSE_TILE(T128x128W8S, TILE_128x128W8, 128, 128, 1, 8, 32, 2, 64, 64)
+#undef ONEPOSE_TILE
 
 template <int EPI, int PRO, class T, int PM, bool WPL = false, int DMA = 0>
 void launch_one(GemmArgs& args, int grid, hipStream_t stream) {
@@ -1343,47 +1363,23 @@ void launch_one(GemmArgs& args, int grid, hipStream_t stream) {
                      args);
 }
 
-// DMA 2 is instantiated only for the combinations that use it (gemm_launch checks the rest):
-// the attention layers' QKV and MLP conv 1 in the bf16 modes
-template <int EPI, int PRO, class T, int PM>
-void launch_adma(GemmArgs& args, int grid, hipStream_t stream) {
-  if constexpr (PRO != PRO_NORM_RELU && (EPI == EPI_QKV || EPI == EPI_STATS))
-    launch_one<EPI, PRO, T, PM, true, 2>(args, grid, stream);
+// Row I of kGemmVariants, launched if it is `want`: the only place a gemm_kernel is instantiated.
+template <size_t I>
+bool launch_row(const GemmVariant& want, GemmArgs& args, int grid, hipStream_t stream) {
+  constexpr GemmVariant v = kGemmVariants[I];
+  if (!gemm_same_variant(v, want)) return false;
+  launch_one<v.epi, v.pro, typename TileOf<v.tile>::type, v.pm, v.wpl, v.dma>(args, grid, stream);
+  return true;
 }
-
-struct TileDims {
-  int bm, bn, bks;
-};
-TileDims tile_dims(int tile) {
-  switch (tile) {
-    case TILE_64x64: return {64, 64, 32};
-    case TILE_32x128: return {32, 128, 32};
-    case TILE_64x32K2: return {64, 32, 64};
-    case TILE_64x128: return {64, 128, 32};
-    case TILE_128x128: return {128, 128, 32};
-    case TILE_128x64W8: return {128, 64, 32};
-    case TILE_32x64W2: return {32, 64, 32};
-    case TILE_32x256W8: return {32, 256, 64};
-    case TILE_128x128W8: return {128, 128, 32};
-
-    default: return {0, 0, 0};
-  }
+template <size_t... I>
+bool launch_variant(const GemmVariant& want, GemmArgs& args, int grid, hipStream_t stream,
+                    std::index_sequence<I...>) {
+  return (launch_row<I>(want, args, grid, stream) || ...);
 }
 
 }  // namespace
 
-int gemm_tile_rows(int tile) { return tile_dims(tile).bm; }
-
-static_assert(gemm_tile_bm(TILE_64x64) == 64 && gemm_tile_bn(TILE_64x64) == 64 &&
-                  gemm_tile_bm(TILE_32x128) == 32 && gemm_tile_bn(TILE_32x128) == 128 &&
-                  gemm_tile_bm(TILE_64x32K2) == 64 && gemm_tile_bn(TILE_64x32K2) == 32 &&
-                  gemm_tile_bm(TILE_64x128) == 64 && gemm_tile_bn(TILE_64x128) == 128 &&
-                  gemm_tile_bm(TILE_128x128) == 128 && gemm_tile_bn(TILE_128x128) == 128 &&
-                  gemm_tile_bm(TILE_128x64W8) == 128 && gemm_tile_bn(TILE_128x64W8) == 64 &&
-                  gemm_tile_bm(TILE_32x64W2) == 32 && gemm_tile_bn(TILE_32x64W2) == 64 &&
-                  gemm_tile_bm(TILE_32x256W8) == 32 && gemm_tile_bn(TILE_32x256W8) == 256 &&
-                  gemm_tile_bm(TILE_128x128W8) == 128 && gemm_tile_bn(TILE_128x128W8) == 128,
-              "gemm.h tile shapes must match tile_dims");
+int gemm_tile_rows(int tile) { return gemm_tile_bm(tile); }
 
 GemmProb gemm_prob(const float* A, int lda, const float* W, int ldw, const float* bias,
                    float* Y, int ldy, int M, int N, int K, int batch) {
@@ -1411,7 +1407,7 @@ GemmProb gemm_prob(const float* A, int lda, const float* W, int ldw, const float
 
 int gemm_launch(int epi, int pro, int tile, GemmArgs& args, hipStream_t stream, int kind,
                 int pm) {
-  const TileDims td = tile_dims(tile);
+  const GemmTileShape td = gemm_tile_shape(tile);
   OP_REQUIRE(td.bm > 0, "gemm: unknown tile %d", tile);
   int grid = 0;
   for (int i = 0; i < 2; ++i) {
@@ -1480,54 +1476,16 @@ int gemm_launch(int epi, int pro, int tile, GemmArgs& args, hipStream_t stream, 
              "gemm: A planes: QKV / MLP conv 1 on the DMA loop (bf16 modes, W planes)");
   OP_REQUIRE(!yplanes || (pm != PM_F32 && (epi == EPI_RESID || epi == EPI_QKV)),
              "gemm: output planes are written by RESID / QKV launches in the bf16 modes");
-#define CASE(E, PR, TI, T, PMV, WP)                                      \
-  if (epi == E && pro == PR && tile == TI && pm == PMV && wpl == WP) {  \
-    prof_pre(kind, stream);                                              \
-    args.stamp = prof_stamp_slot(kind);                                  \
-    if constexpr (WP) {                                                  \
-      if (adma) launch_adma<E, PR, T, PMV>(args, grid, stream);          \
-      else if (dma) launch_one<E, PR, T, PMV, WP, 1>(args, grid, stream); \
-      else launch_one<E, PR, T, PMV, WP, 0>(args, grid, stream);         \
-    } else {                                                             \
-      launch_one<E, PR, T, PMV, WP, 0>(args, grid, stream);              \
-    }                                                                    \
-    prof_post(kind, stream);                                             \
-    OP_LAUNCHED();                                                       \
-    return ONEPOSE_OK;                                                   \
+  const GemmVariant want = {epi, pro, tile, pm, wpl, wpl ? (adma ? 2 : dma ? 1 : 0) : 0};
+  if (gemm_has_variant(want)) {
+    prof_pre(kind, stream);
+    args.stamp = prof_stamp_slot(kind);
+    launch_variant(want, args, grid, stream,
+                   std::make_index_sequence<sizeof(kGemmVariants) / sizeof(kGemmVariants[0])>());
+    prof_post(kind, stream);
+    OP_LAUNCHED();
+    return ONEPOSE_OK;
   }
-  CASE(EPI_QKV, PRO_PLAIN, TILE_32x128, T32x128, PM_F32, false)
-  CASE(EPI_QKV, PRO_PLAIN, TILE_64x128, T64x128, PM_F32, false)
-  CASE(EPI_QKV, PRO_PLAIN, TILE_128x128W8, T128x128W8S, PM_F32, false)
-  CASE(EPI_QKV, PRO_PLAIN, TILE_128x128, T128x128, PM_F32, false)
-  CASE(EPI_STATS, PRO_HEADZ, TILE_64x64, T64x64, PM_F32, false)
-  CASE(EPI_RESID, PRO_NORM_RELU, TILE_64x64, T64x64, PM_F32, false)
-  CASE(EPI_RESID, PRO_NORM_RELU, TILE_64x32K2, T64x32K2, PM_F32, false)
-  CASE(EPI_SCORE, PRO_PLAIN, TILE_64x64, T64x64, PM_F32, false)
-  CASE(EPI_SCORE, PRO_PLAIN, TILE_128x64W8, T128x64W8, PM_F32, false)
-  CASE(EPI_BIAS, PRO_PLAIN, TILE_64x64, T64x64, PM_F32, false)
-  CASE(EPI_BIAS_L2, PRO_PLAIN, TILE_32x256W8, T32x256W8, PM_F32, false)
-  CASE(EPI_ACC, PRO_PLAIN, TILE_64x64, T64x64, PM_F32, false)
-  // attention-layer GEMMs in the bf16 modes: W from the packed bf16 planes (weights rounded /
-  // split on the host, Mf by the KV fold), A rounded / split as the stage is stored
-  CASE(EPI_ACC, PRO_PLAIN, TILE_64x64, T64x64, PM_BF16, true)
-  CASE(EPI_ACC, PRO_PLAIN, TILE_64x64, T64x64, PM_SPLIT3, true)
-  CASE(EPI_QKV, PRO_PLAIN, TILE_32x128, T32x128, PM_BF16, true)
-  CASE(EPI_STATS, PRO_HEADZ, TILE_64x64, T64x64, PM_BF16, true)
-  CASE(EPI_RESID, PRO_NORM_RELU, TILE_64x64, T64x64, PM_BF16, true)
-  CASE(EPI_QKV, PRO_PLAIN, TILE_64x128, T64x128, PM_BF16, true)
-  CASE(EPI_STATS, PRO_HEADZ, TILE_64x128, T64x128, PM_BF16, true)
-  CASE(EPI_RESID, PRO_NORM_RELU, TILE_64x128, T64x128, PM_BF16, true)
-  CASE(EPI_ACC, PRO_PLAIN, TILE_64x128, T64x128, PM_BF16, true)
-  CASE(EPI_RESID, PRO_NORM_RELU, TILE_32x64W2, T32x64W2, PM_SPLIT3, true)
-  CASE(EPI_QKV, PRO_PLAIN, TILE_32x128, T32x128, PM_SPLIT3, true)
-  CASE(EPI_STATS, PRO_HEADZ, TILE_64x64, T64x64, PM_SPLIT3, true)
-  CASE(EPI_STATS, PRO_HEADZ, TILE_128x128W8, T128x128W8S, PM_SPLIT3, true)
-  CASE(EPI_QKV, PRO_PLAIN, TILE_64x128, T64x128, PM_SPLIT3, true)
-  CASE(EPI_RESID, PRO_NORM_RELU, TILE_64x64, T64x64, PM_SPLIT3, true)
-  // final projection and score GEMM in the split mode (activations as W: VALU split)
-  CASE(EPI_SCORE, PRO_PLAIN, TILE_64x64, T64x64, PM_SPLIT3, false)
-  CASE(EPI_BIAS, PRO_PLAIN, TILE_64x64, T64x64, PM_SPLIT3, false)
-#undef CASE
   set_error("gemm: unsupported epilogue/prologue/tile/mode/planes %d/%d/%d/%d/%d", epi, pro, tile,
             pm, (int)wpl);
   return ONEPOSE_ERR_INVALID;

@@ -45,10 +45,27 @@ constexpr int kTileKV = TILE_32x128, kTileMLP1 = TILE_64x64,
 // 64 + l2norm_kernel)
 constexpr int kTileFinalL2 = TILE_32x256W8;
 constexpr int kTileScore = TILE_128x64W8, kScoreBM = 128;
+// Each tile constant names a kernel gemm.hip has (gemm.h kGemmVariants), in the operand mode and
+// loop form (W planes, DMA) its launch asks for: a choice without a kernel does not compile.
+static_assert(gemm_has_variant(EPI_QKV, PRO_PLAIN, kTileKV, PM_F32, false, 0) &&
+                  gemm_has_variant(EPI_STATS, PRO_HEADZ, kTileMLP1, PM_F32, false, 0) &&
+                  gemm_has_variant(EPI_ACC, PRO_PLAIN, kTileMLP1, PM_F32, false, 0) &&
+                  gemm_has_variant(EPI_RESID, PRO_NORM_RELU, kTileMLP2, PM_F32, false, 0) &&
+                  gemm_has_variant(EPI_RESID, PRO_NORM_RELU, kTileMLP2F32, PM_F32, false, 0),
+              "fp32 attention-layer tiles");
+static_assert(gemm_has_variant(EPI_RESID, PRO_NORM_RELU, kTileMLP2, PM_BF16, true, 0) &&
+                  gemm_has_variant(EPI_RESID, PRO_NORM_RELU, kTileMLP2, PM_SPLIT3, true, 1),
+              "MLP conv 2 on W planes: register-staged in bf16, the DMA loop in the split mode");
+static_assert(gemm_has_variant(EPI_BIAS_L2, PRO_PLAIN, kTileFinalL2, PM_F32, false, 0) &&
+                  gemm_has_variant(EPI_BIAS, PRO_PLAIN, kTileFinal, PM_SPLIT3, false, 0) &&
+                  gemm_has_variant(EPI_SCORE, PRO_PLAIN, kTileScore, PM_F32, false, 0),
+              "final projection and score tiles");
 // mlp2 in the split mode below 4 tiles per CU: 32 x 64 on 2 waves (config 2: 640 workgroups
 // instead of 320; 0.231 -> 0.213 ms per frame); the bf16 mode keeps 64 x 64 (32 x 64 measured
 // 0.110 -> 0.117 at config 2 and 0.154 -> 0.166 at config 5, profiles/r04/planes/)
 constexpr int kTileMLP2Split = TILE_32x64W2;
+static_assert(gemm_has_variant(EPI_RESID, PRO_NORM_RELU, kTileMLP2Split, PM_SPLIT3, true, 1),
+              "split-mode MLP conv 2 tile");
 constexpr int kFusedFoldMaxBatch = 4;   // kv_fold up to this batch, kv_reduce + m_fold above
 constexpr int kMlp2WideTiles = 1024;    // fp32 mlp2: 64x64 tiles from this many (4 per CU)
 constexpr int kQkvWideTiles = 256;      // fp32 qkv: 64x128 tiles from this many 64-row tiles
@@ -1265,6 +1282,16 @@ int mlp1_tile(int pm) {
   return pm == PM_BF16 ? kTileBf16Mlp1 : pm == PM_SPLIT3 ? kTileSplitMlp1 : kTileMLP1;
 }
 int mlp1_acc_tile(int pm) { return pm == PM_BF16 ? kTileBf16 : kTileMLP1; }
+// The bf16 modes' producers always write activation planes (Forward::npl), so QKV and MLP conv 1
+// run the DMA-2 loop on kTileBf16 / kTileBf16Mlp1 / kTileSplitMlp1; only the object prepare's
+// EPI_ACC launch (mlp1_acc_tile, no A planes) takes DMA 1.
+static_assert(gemm_has_variant(EPI_QKV, PRO_PLAIN, kTileBf16, PM_BF16, true, 2) &&
+                  gemm_has_variant(EPI_QKV, PRO_PLAIN, kTileBf16, PM_SPLIT3, true, 2) &&
+                  gemm_has_variant(EPI_STATS, PRO_HEADZ, kTileBf16Mlp1, PM_BF16, true, 2) &&
+                  gemm_has_variant(EPI_STATS, PRO_HEADZ, kTileSplitMlp1, PM_SPLIT3, true, 2) &&
+                  gemm_has_variant(EPI_ACC, PRO_PLAIN, kTileBf16, PM_BF16, true, 1) &&
+                  gemm_has_variant(EPI_ACC, PRO_PLAIN, kTileMLP1, PM_SPLIT3, true, 1),
+              "bf16 / split-mode QKV, MLP conv 1 and acc0 tiles");
 // make_plan sizes MLP conv 1's InstanceNorm partials (stats rows `str`), its arrival counters
 // (kCntPerSide column blocks) and group partials once for every precision: each precision's
 // MLP conv 1 tile must have those rows and at most that many column blocks over N = 512.
@@ -1289,6 +1316,9 @@ int qkv_tile_for(int n3, int B) {
   // +0.3% at 300 steps / level at 20 on the confirming run, profiles/r05/qconf/: a marginal gain)
   return t64 >= kQkvWiderTiles ? TILE_128x128 : t64 >= kQkvWideTiles ? TILE_128x128W8 : kTileKV;
 }
+static_assert(gemm_has_variant(EPI_QKV, PRO_PLAIN, TILE_128x128, PM_F32, false, 0) &&
+                  gemm_has_variant(EPI_QKV, PRO_PLAIN, TILE_128x128W8, PM_F32, false, 0),
+              "qkv_tile_for's wide tiles");
 
 bool valid_precision(int p) {
   return p == ONEPOSE_PREC_FP32 || p == ONEPOSE_PREC_BF16_ATTN || p == ONEPOSE_PREC_FP32_SPLIT;
@@ -2140,6 +2170,8 @@ int stage_score(Forward& f) {
   // score tile: 128 x 64 on 8 waves in fp32 (K = 256 is short; fewer operand loads per FLOP
   // than 64 x 64), 64 x 64 in the split mode (its LDS images are three bf16 planes)
   const int score_tile = f.pm_out == PM_F32 ? kTileScore : TILE_64x64;
+  static_assert(gemm_has_variant(EPI_SCORE, PRO_PLAIN, TILE_64x64, PM_SPLIT3, false, 0),
+                "split-mode score tile");
   GemmArgs a;
   a.nprob = 1;
   a.p[0] = gemm_prob(p.f2, 256, p.f3, 256, nullptr, f.S, c.n3, c.n1, c.n3, 256, c.batch);

@@ -762,6 +762,11 @@ struct SgPlan {
   size_t bytes;
 };
 constexpr int kSgScoreTile = TILE_128x64W8;
+// the forward's GEMMs name kernels gemm.hip has (gemm.h kGemmVariants): fp32, register-staged
+static_assert(gemm_has_variant(EPI_SCORE, PRO_PLAIN, kSgScoreTile, PM_F32, false, 0) &&
+                  gemm_has_variant(EPI_BIAS, PRO_PLAIN, TILE_64x64, PM_F32, false, 0) &&
+                  gemm_has_variant(EPI_RESID, PRO_NORM_RELU, TILE_64x64, PM_F32, false, 0),
+              "SuperGlue's GEMM tiles");
 
 SgPlan sg_plan(void* ws, int batch, int n0, int n1) {
   Carve c(ws);
