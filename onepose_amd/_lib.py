@@ -4,15 +4,22 @@ This is the binding a maintainer of the reference would drop in
 pointers from ``torch.Tensor.data_ptr()``, the current HIP stream, and an int status mapped
 to exceptions.  The library is loaded from the package directory (built in-tree by
 ``onepose_amd.build``); there is no fallback -- if it is missing, every call raises.
+
+The header is the one source of the signatures: ``SIGNATURES`` is parsed from it at import,
+``load()`` types every function from it, and ``call`` / ``run`` take their arguments by the
+header's parameter names.
 """
 from __future__ import annotations
 
 import ctypes
+import keyword
 import os
+import re
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # ONEPOSE_LIB: an alternative in-tree build of the same library (A/B measurement, tools/ab.sh)
 LIB_PATH = os.environ.get("ONEPOSE_LIB") or os.path.join(_HERE, "libonepose_hip.so")
+HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "onepose_hip.h")
 
 c_int, c_int64, c_size_t, c_float, c_double = (ctypes.c_int, ctypes.c_int64, ctypes.c_size_t,
                                                ctypes.c_float, ctypes.c_double)
@@ -20,6 +27,7 @@ c_void_p, c_char_p = ctypes.c_void_p, ctypes.c_char_p
 
 # onepose_allgather_fn: int (*)(size_t bytes_per_rank, void* stream, void* user)
 ALLGATHER_FN = ctypes.CFUNCTYPE(c_int, c_size_t, c_void_p, c_void_p)
+# the constants below mirror the header's enums (tests/test_binding.py compares them)
 ABI_VERSION = 9
 DEVERR_STALE_CACHE = 1   # ONEPOSE_DEVERR_STALE_CACHE
 STAGE_INPUTS, STAGE_LAYER0, STAGE_FINAL, STAGE_SCORE, STAGE_WINNERS = 0, 1, 13, 14, 15  # ABI 6
@@ -28,210 +36,96 @@ WHERE_WORKSPACE, WHERE_OBJECT_CACHE = 0, 1   # ONEPOSE_WHERE_*
 OBJ_GAT_TABLES = 1   # ONEPOSE_OBJ_GAT_TABLES
 DT_F32, DT_F16 = 0, 1   # ONEPOSE_DT_*
 
-# name -> (restype, argtypes); mirrors include/onepose_hip.h
-PROTOTYPES = {
-    "onepose_last_error": (c_char_p, []),
-    "onepose_abi_version": (c_int, []),
-    "onepose_device_errors": (c_int, [c_int, ctypes.POINTER(ctypes.c_uint)]),
-    "onepose_matcher_num_tensors": (c_int, []),
-    "onepose_matcher_tensor_name": (c_char_p, [c_int]),
-    "onepose_matcher_tensor_numel": (c_int64, [c_int]),
-    "onepose_matcher_packed_bytes": (c_size_t, []),
-    "onepose_matcher_pack": (c_int, [ctypes.POINTER(c_void_p), c_int, c_void_p]),
-    "onepose_match_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int]),
-    "onepose_match_workspace_bytes_ex": (c_size_t, [c_int, c_int, c_int, c_int, c_int, c_int]),
-    "onepose_prepare_leaves_dt": (c_int, [c_void_p, c_int, c_int64, c_int, c_int, c_int, c_void_p,
-                                          c_void_p]),
-    "onepose_match_dt": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64,
-                                 c_int, c_int, c_int, c_int, c_int, c_float, c_float, c_int,
-                                 c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
-                                 c_void_p, c_size_t, c_void_p]),
-    "onepose_object_prepare_dt": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_int,
-                                          c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
-    "onepose_match_cached_dt": (c_int, [c_void_p, c_void_p, c_int, c_int64, c_void_p, c_void_p,
-                                        c_int64, c_int, c_int, c_int, c_int, c_float, c_float,
-                                        c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
-                                        c_void_p, c_void_p, c_size_t, c_void_p]),
-    "onepose_match_cached_stages": (c_int, [c_void_p, c_void_p, c_int, c_int64, c_void_p,
-                                            c_void_p, c_int64, c_int, c_int, c_int, c_int,
-                                            c_float, c_float, c_int, c_int, c_void_p, c_void_p,
-                                            c_void_p, c_void_p, c_void_p, c_void_p, c_size_t,
-                                            c_int, c_int, c_void_p]),
-    "onepose_match_workspace_region": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, c_int,
-                                               c_int, ctypes.POINTER(c_int),
-                                               ctypes.POINTER(c_size_t),
-                                               ctypes.POINTER(c_size_t)]),
-    "onepose_match": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64,
-                              c_int, c_int, c_int, c_int, c_float, c_float,
-                              c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
-                              c_void_p, c_size_t, c_void_p]),
-    "onepose_match_prepared": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_void_p,
-                                       c_int64, c_int, c_int, c_int, c_int, c_float, c_float,
-                                       c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
-                                       c_void_p, c_size_t, c_void_p]),
-    "onepose_match_ex": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_void_p,
-                                 c_int64, c_int, c_int, c_int, c_int, c_float, c_float, c_int,
-                                 c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
-                                 c_void_p, c_size_t, c_void_p]),
-    "onepose_match_prepared_ex": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int64,
-                                          c_void_p, c_int64, c_int, c_int, c_int, c_int, c_float,
-                                          c_float, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
-                                          c_void_p, c_void_p, c_size_t, c_void_p]),
-    "onepose_object_cache_bytes": (c_size_t, [c_int, c_int, c_int]),
-    "onepose_object_cache_bytes_ex": (c_size_t, [c_int, c_int, c_int, c_int]),
-    "onepose_object_prepare_workspace_bytes": (c_size_t, [c_int, c_int]),
-    "onepose_object_prepare": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,
-                                       c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
-    "onepose_object_release": (None, [c_void_p]),
-    "onepose_match_cached": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int64,
-                                     c_int, c_int, c_int, c_int, c_float, c_float, c_int, c_int,
-                                     c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
-                                     c_void_p, c_size_t, c_void_p]),
-    "onepose_shard_range": (None, [c_int, c_int, c_int, ctypes.POINTER(c_int),
-                                   ctypes.POINTER(c_int)]),
-    "onepose_match_sharded_xchg_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
-    "onepose_match_sharded_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int,
-                                                         c_int, c_int]),
-    "onepose_match_sharded": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_void_p,
-                                      c_int64, c_int, c_int, c_int, c_int, c_int, c_int,
-                                      c_float, c_float, c_int, c_void_p, c_void_p, c_size_t,
-                                      ALLGATHER_FN, c_void_p, c_void_p, c_void_p, c_void_p,
-                                      c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
-    "onepose_leaves_prepared_bytes": (c_size_t, [c_int, c_int, c_int]),
-    "onepose_prepare_leaves": (c_int, [c_void_p, c_int64, c_int, c_int, c_int, c_void_p,
-                                       c_void_p]),
-    "onepose_sample_descriptors": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int,
-                                           c_int, c_int, c_void_p, c_void_p]),
-    "onepose_select_correspondences": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int64,
-                                               c_int, c_int, c_int, c_double, c_void_p, c_void_p,
-                                               c_void_p, c_void_p]),
-    "onepose_pnp_max_points": (c_int, []),   # ABI 8
-    "onepose_pnp_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
-    "onepose_pnp_ransac": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int64, c_int,
-                                   c_double, c_float, c_int, c_double, c_void_p, c_void_p,
-                                   c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
-    "onepose_pose_errors": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p,
-                                    c_void_p, c_void_p]),
-    "onepose_pose_stage": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int, c_int,
-                                   c_int, c_double, c_void_p, c_int64, c_float, c_int, c_double,
-                                   c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p,
-                                   c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
-                                   c_void_p, c_size_t, c_void_p]),
-    "onepose_superpoint_num_tensors": (c_int, []),
-    "onepose_superpoint_tensor_name": (c_char_p, [c_int]),
-    "onepose_superpoint_packed_bytes": (c_size_t, []),
-    "onepose_superpoint_pack": (c_int, [ctypes.POINTER(c_void_p), c_int, c_void_p]),
-    "onepose_superpoint_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
-    "onepose_superpoint": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_float, c_int,
-                                   c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
-                                   c_void_p, c_void_p, c_size_t, c_void_p]),
-    "onepose_superpoint_detect_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
-    "onepose_superpoint_detect": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_float,
-                                          c_int, c_int, c_int, c_void_p, c_void_p, c_void_p,
-                                          c_void_p, c_void_p, c_size_t, c_void_p]),
-    "onepose_superpoint_layer_out_floats": (c_size_t, [c_int, c_int, c_int]),   # ABI 9
-    "onepose_superpoint_layer": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_void_p,
-                                         c_void_p]),
-    "onepose_superglue_version": (c_int, []),
-    "onepose_superglue_num_tensors": (c_int, []),
-    "onepose_superglue_tensor_name": (c_char_p, [c_int]),
-    "onepose_superglue_tensor_numel": (c_int64, [c_int]),
-    "onepose_superglue_packed_bytes": (c_size_t, []),
-    "onepose_superglue_pack": (c_int, [ctypes.POINTER(c_void_p), c_int, c_void_p]),
-    "onepose_superglue_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
-    "onepose_superglue_match": (c_int, [c_void_p,
-                                        c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64,
-                                        c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64,
-                                        c_int, c_int, c_int, c_int, c_int, c_int, c_int,
-                                        c_int, c_float, c_int,
-                                        c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
-                                        c_void_p, c_size_t, c_void_p]),
-    "onepose_log_optimal_transport_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
-    "onepose_log_optimal_transport": (c_int, [c_void_p, c_int64, c_int, c_int, c_int, c_float,
-                                              c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
-    "onepose_mha_softmax": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64,
-                                    c_int, c_int, c_int, c_void_p, c_int64, c_void_p]),
-    "onepose_detector_version": (c_int, []),
-    "onepose_affine_partial_max_points": (c_int, []),
-    "onepose_affine_partial_workspace_bytes": (c_size_t, [c_int, c_int]),
-    "onepose_affine_partial_ransac": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int,
-                                              c_double, c_int, c_double, c_int,
-                                              c_void_p, c_void_p, c_void_p, c_void_p,
-                                              c_void_p, c_size_t, c_void_p]),
-    "onepose_detect_stage": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p,
-                                     c_int, c_int, c_int, c_int, c_int,
-                                     c_double, c_int, c_double, c_int, c_int,
-                                     c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
-                                     c_void_p, c_void_p, c_void_p,
-                                     c_void_p, c_size_t, c_void_p]),
-    "onepose_crop_resize": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_int,
-                                    c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
-    "onepose_nn_version": (c_int, []),
-    "onepose_nn_match_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
-    "onepose_nn_match": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int,
-                                 c_int, c_int, c_int, c_int, c_double, c_double, c_int,
-                                 c_void_p, c_void_p, c_void_p, c_void_p,
-                                 c_void_p, c_size_t, c_void_p]),
-    "onepose_nn_similarity_top2": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int,
-                                           c_int, c_int, c_int, c_int,
-                                           c_void_p, c_size_t, c_void_p]),
-    "onepose_ba_version": (c_int, []),
-    "onepose_ba_max_active_cameras": (c_int, []),
-    "onepose_ba_index_bytes": (c_size_t, [c_int64, c_int, c_int]),
-    "onepose_ba_build_index": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_int, c_void_p,
-                                       c_size_t, ctypes.POINTER(c_int), ctypes.POINTER(c_int)]),
-    "onepose_ba_workspace_bytes": (c_size_t, [c_int64, c_int, c_int]),
-    "onepose_ba_solve": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
-                                 c_int64, c_int, c_int, c_int, c_int, c_int, c_int, c_double,
-                                 c_void_p, c_void_p, c_size_t, c_void_p]),
-    "onepose_ba_linearize": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
-                                     c_int64, c_int, c_int, c_void_p, c_void_p, c_void_p,
-                                     c_void_p, c_void_p]),
-    "onepose_triangulate": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_double,
-                                    c_double, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
-                                    c_void_p]),
-    "onepose_lk_version": (c_int, []),
-    "onepose_lk_levels": (c_int, [c_int, c_int, c_int, c_int]),
-    "onepose_lk_pyramid_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
-    "onepose_lk_pyramid_layout": (c_int, [c_int, c_int, c_int, c_int, c_int,
-                                          ctypes.POINTER(c_int), ctypes.POINTER(c_int),
-                                          ctypes.POINTER(c_int64), ctypes.POINTER(c_int64)]),
-    "onepose_lk_build_pyramid": (c_int, [c_void_p, c_int64, c_int, c_int, c_int, c_int, c_int,
-                                         c_int, c_void_p, c_void_p]),
-    "onepose_lk_track": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_int,
-                                 c_int, c_int, c_int, c_int, c_int, c_int, c_float, c_float,
-                                 c_void_p, c_void_p, c_void_p]),
-    "onepose_objbuild_version": (c_int, []),
-    "onepose_filter_points": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p,
-                                      c_void_p, c_void_p, c_void_p]),
-    "onepose_radius_neighbours": (c_int, [c_void_p, c_int, c_int, c_double, c_void_p, c_void_p,
-                                          c_int64, c_void_p, c_void_p]),
-    "onepose_merge_greedy": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p,
-                                     c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
-    "onepose_lift_descriptors": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_int, c_void_p,
-                                         c_void_p, c_int, c_void_p, c_int, c_int, c_void_p,
-                                         c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
-    "onepose_gather_leaves": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_void_p,
-                                      c_void_p]),
-    "onepose_sfm_version": (c_int, []),
-    "onepose_sfm_max_track": (c_int, []),
-    "onepose_track_components": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p,
-                                         c_void_p]),
-    "onepose_tracks_triangulate": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p,
-                                           c_int, c_int, c_double, c_double, c_void_p, c_void_p,
-                                           c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
-    "onepose_profile_begin": (c_int, [ctypes.c_uint64, c_int]),
-    "onepose_profile_begin_device": (c_int, [ctypes.c_uint64]),
-    "onepose_profile_end_device": (c_int, [c_void_p, c_void_p, c_int]),
-    "onepose_profile_end": (c_int, [c_void_p, c_void_p, c_int, c_void_p]),
-    "onepose_profile_kind_name": (c_char_p, [c_int]),
-}
-
-_lib = None
-
 
 class OnePoseError(RuntimeError):
     pass
+
+
+_VALUE_TYPES = {"int": c_int, "int64_t": c_int64, "size_t": c_size_t, "float": c_float,
+                "double": c_double, "unsigned": ctypes.c_uint, "uint64_t": ctypes.c_uint64,
+                "onepose_allgather_fn": ALLGATHER_FN}
+_DECL = re.compile(r"(.+?)\b(onepose_\w+)\s*\((.*)\)", re.S)
+
+
+def parse_header(text):
+    """The header's declarations and enums:
+    ({name: (restype, ((param_name, ctype), ...))}, {ENUM_NAME: value}).
+    Every pointer is c_void_p (a ``const char*`` return c_char_p).  Strict: a statement that is
+    not a declaration, or a type that has no ctype here, raises and names the declaration."""
+    text = re.sub(r"/\*.*?\*/", " ", text, flags=re.S)
+    text = re.sub(r'^\s*(#.*|extern "C" \{|\})$', " ", text, flags=re.M)   # (extern "C"'s braces)
+    enums = {}
+
+    def take_enum(m):
+        for item in m.group(1).split(","):
+            name, eq, value = (x.strip() for x in item.partition("="))
+            if not eq or not re.fullmatch(r"\w+", name):
+                raise OnePoseError(f"onepose_hip.h: enum item {item.strip()!r} is not NAME = value")
+            enums[name] = int(value, 0)
+        return " "
+    text = re.sub(r"\benum\s*\{(.*?)\}\s*;", take_enum, text, flags=re.S)
+
+    def take_typedef(m):
+        if m.group(1) not in _VALUE_TYPES:
+            raise OnePoseError(f"onepose_hip.h: typedef {m.group(1)} has no ctypes type")
+        return " "
+    text = re.sub(r"\btypedef\b[^;]*?\(\s*\*\s*(\w+)\s*\)[^;]*;", take_typedef, text)
+
+    def ctype(decl, what, name):
+        if "*" in decl:
+            return c_void_p
+        t = re.sub(r"\bconst\b", " ", decl).strip()
+        if t not in _VALUE_TYPES:
+            raise OnePoseError(f"onepose_hip.h: {name}: {what} type {decl.strip()!r} has no "
+                               "ctypes type")
+        return _VALUE_TYPES[t]
+
+    signatures = {}
+    for stmt in filter(None, (s.strip() for s in text.split(";"))):
+        m = _DECL.fullmatch(stmt)
+        if m is None:
+            raise OnePoseError(f"onepose_hip.h: not a declaration: {' '.join(stmt.split())!r}")
+        ret, name, params = m.group(1).strip(), m.group(2), m.group(3).strip()
+        if name in signatures:
+            raise OnePoseError(f"onepose_hip.h: {name} is declared twice")
+        if re.sub(r"\s+", "", ret) == "constchar*":
+            restype = c_char_p
+        elif ret == "void":
+            restype = None
+        elif "*" in ret:
+            raise OnePoseError(f"onepose_hip.h: {name}: return type {ret!r} has no ctypes type")
+        else:
+            restype = ctype(ret, "return", name)
+        args = []
+        for p in ([] if params == "void" else params.split(",")):
+            pm = re.fullmatch(r"\s*(.*?[\s*])(\w+)\s*", p, re.S)
+            if pm is None:
+                raise OnePoseError(f"onepose_hip.h: {name}: parameter {p.strip()!r} has no name")
+            args.append((pm.group(2), ctype(pm.group(1), f"parameter {pm.group(2)}'s", name)))
+        signatures[name] = (restype, tuple(args))
+    return signatures, enums
+
+
+def _read_header():
+    try:
+        with open(HEADER_PATH) as f:
+            return f.read()
+    except OSError as e:
+        raise OnePoseError(f"{HEADER_PATH} is missing ({e.strerror}): onepose_amd reads the "
+                           "library's signatures from it (in-tree layout)") from None
+
+
+# name -> (restype, ((param_name, ctype), ...)), and the header's enum values
+SIGNATURES, ENUMS = parse_header(_read_header())
+# name -> (restype, [argtypes])
+PROTOTYPES = {name: (res, [t for _, t in params]) for name, (res, params) in SIGNATURES.items()}
+# name -> (keyword names in order, indices of the pointer parameters); a parameter named like
+# a Python keyword takes a trailing underscore (onepose_affine_partial_ransac's from_)
+_ORDER = {name: (tuple(n + "_" * keyword.iskeyword(n) for n, _ in params),
+                 tuple(i for i, (_, t) in enumerate(params) if t is c_void_p))
+          for name, (_, params) in SIGNATURES.items()}
+
+_lib = None
 
 
 def load():
@@ -259,11 +153,39 @@ def load():
     return _lib
 
 
+def call(name, **args):
+    """lib.<name>(...) with the arguments given by the header's parameter names; returns the
+    function's raw result.  A tensor in a pointer slot goes as its data_ptr(), None as a null
+    pointer.  Every parameter must be given (no defaults, `stream` included) and no other: a
+    missing or unknown one raises TypeError before the library is entered.  Nothing is
+    allocated or synchronised, so it can be used inside a graph capture."""
+    try:
+        names, pointers = _ORDER[name]
+    except KeyError:
+        raise TypeError(f"{name} is not declared in onepose_hip.h") from None
+    try:
+        vals = [args[n] for n in names]
+    except KeyError as e:
+        raise TypeError(f"{name}: missing argument {e.args[0]!r}") from None
+    if len(args) != len(names):
+        raise TypeError(f"{name}: unknown argument {sorted(set(args) - set(names))[0]!r}")
+    for i in pointers:
+        if hasattr(vals[i], "data_ptr"):
+            vals[i] = vals[i].data_ptr()
+    return getattr(_lib or load(), name)(*vals)
+
+
+def run(name, **args) -> None:
+    """call() for a function that returns a status: raises OnePoseError unless it is 0."""
+    check(call(name, **args), name)
+
+
 def workspace_bytes(lib, B, n1, n3, L, with_conf, precision) -> int:
     """onepose_match_workspace_bytes_ex (this precision's need), or the every-precision query
     on an older A/B build without it."""
     if hasattr(lib, "onepose_match_workspace_bytes_ex"):
-        return lib.onepose_match_workspace_bytes_ex(B, n1, n3, L, int(with_conf), int(precision))
+        return call("onepose_match_workspace_bytes_ex", batch=B, n1=n1, n3=n3, num_leaf=L,
+                    with_conf=int(with_conf), precision=int(precision))
     return lib.onepose_match_workspace_bytes(B, n1, n3, L, int(with_conf))
 
 
@@ -277,10 +199,10 @@ def workspace_region(lib, B, n1, n3, L, with_conf, precision, region, after_stag
     """onepose_match_workspace_region: (where, byte offset, byte count) of `region` (REGION_*)
     after the stages up to `after_stage` of a cached forward; where is WHERE_*."""
     where, off, nbytes = c_int(0), c_size_t(0), c_size_t(0)
-    check(lib.onepose_match_workspace_region(B, n1, n3, L, int(with_conf), int(precision),
-                                             int(region), int(after_stage), ctypes.byref(where),
-                                             ctypes.byref(off), ctypes.byref(nbytes)),
-          "match_workspace_region")
+    run("onepose_match_workspace_region", batch=B, n1=n1, n3=n3, num_leaf=L,
+        with_conf=int(with_conf), precision=int(precision), region=int(region),
+        after_stage=int(after_stage), where=ctypes.byref(where), offset=ctypes.byref(off),
+        bytes=ctypes.byref(nbytes))
     return int(where.value), int(off.value), int(nbytes.value)
 
 

@@ -63,11 +63,10 @@ def affine_partial_ransac(from_pts, to_pts, counts, threshold=6.0, max_iters=200
            "status": torch.empty(B, dtype=torch.int32, device=dev)}
     with torch.cuda.device(dev):
         ws = _ransac_workspace(lib, B, P, dev)
-        _lib.check(lib.onepose_affine_partial_ransac(
-            f.data_ptr(), t.data_ptr(), c.data_ptr(), P, B, float(threshold), int(max_iters),
-            float(confidence), int(refine_iters), out["affine"].data_ptr(),
-            out["inlier_mask"].data_ptr(), out["n_inliers"].data_ptr(), out["status"].data_ptr(),
-            ws.data_ptr(), ws.numel(), _lib.stream_ptr(dev)), "onepose_affine_partial_ransac")
+        _lib.run("onepose_affine_partial_ransac", from_=f, to=t, counts=c, max_points=P, batch=B,
+                 threshold=float(threshold), max_iters=int(max_iters),
+                 confidence=float(confidence), refine_iters=int(refine_iters), **out,
+                 workspace=ws, workspace_bytes=ws.numel(), stream=_lib.stream_ptr(dev))
     out["iters"] = ws[:4 * B].view(torch.int32)
     return out
 
@@ -104,14 +103,12 @@ def detect_stage(matches0, counts0, kpts0, kpts1, db_hw, query_hw, threshold=6.0
            "best_bbox": torch.empty(4, **i32)}
     with torch.cuda.device(dev):
         ws = _ransac_workspace(lib, B, n0, dev)
-        _lib.check(lib.onepose_detect_stage(
-            m.data_ptr(), _lib.ptr(c0), k0.data_ptr(), k1.data_ptr(), 0 if shared else n1 * 2,
-            hw.data_ptr(), B, n0, n1, int(query_hw[0]), int(query_hw[1]), float(threshold),
-            int(max_iters), float(confidence), int(refine_iters), int(rank_mode),
-            out["counts"].data_ptr(), out["mpts"].data_ptr(), out["affine"].data_ptr(),
-            out["inlier_mask"].data_ptr(), out["n_inliers"].data_ptr(), out["status"].data_ptr(),
-            out["bbox"].data_ptr(), out["best_view"].data_ptr(), out["best_bbox"].data_ptr(),
-            ws.data_ptr(), ws.numel(), _lib.stream_ptr(dev)), "onepose_detect_stage")
+        _lib.run("onepose_detect_stage", matches0=m, counts0=c0, kpts0=k0, kpts1=k1,
+                 kpts1_bstride=0 if shared else n1 * 2, db_hw=hw, batch=B, n0=n0, n1=n1,
+                 query_h=int(query_hw[0]), query_w=int(query_hw[1]), threshold=float(threshold),
+                 max_iters=int(max_iters), confidence=float(confidence),
+                 refine_iters=int(refine_iters), rank_mode=int(rank_mode), **out,
+                 workspace=ws, workspace_bytes=ws.numel(), stream=_lib.stream_ptr(dev))
     out["iters"] = ws[:4 * B].view(torch.int32)
     return out
 
@@ -120,7 +117,6 @@ def crop_resize(image_u8, bbox, K=None, crop_size=512):
     """``onepose_crop_resize``: image [h, w] uint8 and bbox [4] int32 on the GPU, K [3, 3] float64
     (GPU) or None -> dict of device tensors: crop_u8 [S, S], crop_f32 [S, S] = u8 / 255, K_crop
     [3, 3] float64 (absent without K), crop_status [1] int32.  No host synchronisation."""
-    lib = _lib.load()
     dev = image_u8.device
     if dev.type != "cuda":
         raise RuntimeError("onepose_amd.detector runs on a ROCm GPU only")
@@ -137,10 +133,8 @@ def crop_resize(image_u8, bbox, K=None, crop_size=512):
         Kd = K.to(torch.float64).contiguous()
         out["K_crop"] = torch.empty(3, 3, dtype=torch.float64, device=dev)
     with torch.cuda.device(dev):
-        _lib.check(lib.onepose_crop_resize(
-            img.data_ptr(), img.shape[0], img.shape[1], box.data_ptr(), _lib.ptr(Kd), S,
-            out["crop_u8"].data_ptr(), out["crop_f32"].data_ptr(), _lib.ptr(out.get("K_crop")),
-            out["crop_status"].data_ptr(), _lib.stream_ptr(dev)), "onepose_crop_resize")
+        _lib.run("onepose_crop_resize", image=img, h=img.shape[0], w=img.shape[1], bbox=box, K=Kd,
+                 crop_size=S, **{"K_crop": None, **out}, stream=_lib.stream_ptr(dev))
     return out
 
 

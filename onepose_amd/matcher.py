@@ -26,6 +26,7 @@ import torch
 import torch.nn as nn
 
 from . import _lib
+from .prepared import PreparedObject
 
 SUPPORTED = {"include_self": True, "additional": False, "with_linear_transform": False}
 
@@ -240,43 +241,16 @@ class GATsSuperGlue(nn.Module):
         key = (str(dev), self.precision, half, n3, nleaf, ident(t3), ident(tl), w.data_ptr(),
                self._packed_key)
         cur = self.__dict__.get("_obj")
-        if cur is not None and cur["key"] == key:
-            return cur
-        self._release_resident()
-        lib = _lib.load()
-        dt = _lib.DT_F16 if half else _lib.DT_F32
-        f32 = dict(dtype=torch.float32, device=dev)
-        s = _lib.stream_ptr(dev)
-        with torch.cuda.device(dev):
-            pm = torch.empty(n3 * nleaf * 256, **f32)
-            _lib.check(lib.onepose_prepare_leaves_dt(db.data_ptr(), dt, 0, 1, n3, nleaf,
-                                                     pm.data_ptr(), s), "prepare_leaves")
-            cache = torch.empty(_lib.object_cache_bytes(lib, n3, nleaf, 0, self.precision) // 4,
-                                **f32)
-            wsb = lib.onepose_object_prepare_workspace_bytes(n3, nleaf)
-            ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
-            _lib.check(lib.onepose_object_prepare_dt(w.data_ptr(), d3.data_ptr(), dt, pm.data_ptr(),
-                                                     n3, nleaf, self.precision, 0,
-                                                     cache.data_ptr(), ws.data_ptr(), wsb, s),
-                       "object_prepare")
-            # a forward on another stream waits for the prepare (_run)
-            ready = torch.cuda.Event()
-            ready.record(torch.cuda.current_stream(dev))
-        del ws   # (stream-ordered: the allocator hands it out only behind the prepare)
-        self._obj = {"key": key, "refs": (t3, tl, d3, db), "pm": pm, "cache": cache,
-                     "ready": ready, "stream": torch.cuda.current_stream(dev)}
-        return self._obj
+        if cur is None or cur["key"] != key:
+            self._release_resident()
+            cur = self._obj = {"key": key, "refs": (t3, tl, d3, db),
+                               "prepared": PreparedObject(w, d3, db, self.precision)}
+        return cur["prepared"]
 
     def _release_resident(self):
         cur = self.__dict__.pop("_obj", None)
         if cur is not None:
-            try:
-                _lib.load().onepose_object_release(cur["cache"].data_ptr())
-            except Exception:
-                pass
-
-    def __del__(self):
-        self._release_resident()
+            cur["prepared"].release()
 
     def _run(self, d2, s2, d3, s3, db, sl, B, n1, n3, nleaf, dev, obj=None):
         lib = _lib.load()
@@ -290,40 +264,28 @@ class GATsSuperGlue(nn.Module):
             ws_bytes = _lib.workspace_bytes(lib, B, n1, n3, nleaf, True, self.precision)
             ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
             dt = _lib.DT_F16 if d2.dtype == torch.float16 else _lib.DT_F32
+            args = dict(packed_weights=w, desc2d=d2, desc2d_bstride=s2, batch=B, n1=n1, n3=n3,
+                        num_leaf=nleaf, scale_factor=float(_hp(self.hparams, "scale_factor")),
+                        match_threshold=float(_hp(self.hparams, "match_threshold")),
+                        precision=self.precision, matches0=m0, matches1=m1, mscores0=ms0,
+                        mscores1=ms1, conf=conf, workspace=ws, workspace_bytes=ws_bytes,
+                        stream=_lib.stream_ptr(dev))
             if obj is not None:
-                cur = torch.cuda.current_stream(dev)
-                if cur != obj["stream"]:
-                    # built on another stream: order this forward behind the prepare, and tell
-                    # the allocator the cache is in use here too
-                    cur.wait_event(obj["ready"])
-                    obj["cache"].record_stream(cur)
-                    obj["pm"].record_stream(cur)
-                rc = lib.onepose_match_cached_dt(
-                    w.data_ptr(), d2.data_ptr(), dt, s2, obj["cache"].data_ptr(),
-                    obj["pm"].data_ptr(), 0, B, n1, n3, nleaf,
-                    float(_hp(self.hparams, "scale_factor")),
-                    float(_hp(self.hparams, "match_threshold")), self.precision, 0,
-                    m0.data_ptr(), m1.data_ptr(), ms0.data_ptr(), ms1.data_ptr(), conf.data_ptr(),
-                    ws.data_ptr(), ws_bytes, _lib.stream_ptr(dev))
-                _lib.check(rc, "onepose_match_cached")
-                return ({"matches0": m0[0], "matches1": m1[0],
-                         "matching_scores0": ms0[0], "matching_scores1": ms1[0]}, conf)
-            # (an older A/B build named by ONEPOSE_LIB has only the fp32 entry point, which
-            # would read fp16 descriptors as fp32)
-            if hasattr(lib, "onepose_match_dt"):
-                call = lib.onepose_match_dt
-            elif dt == _lib.DT_F16:
-                raise _lib.OnePoseError("this libonepose_hip build (ABI < 4) has no fp16 "
-                                        "descriptor entry point (onepose_match_dt)")
+                # built on another stream: this forward runs behind the prepare
+                obj.use_on(torch.cuda.current_stream(dev))
+                _lib.run("onepose_match_cached_dt", desc_dtype=dt, object_cache=obj.cache,
+                         leaves_prepared=obj.leaves_pm, prepared_bstride=0, object_flags=0, **args)
             else:
-                call = lambda *a: lib.onepose_match_ex(*a[:7], *a[8:])
-            rc = call(
-                w.data_ptr(), d2.data_ptr(), s2, d3.data_ptr(), s3, db.data_ptr(), sl, dt,
-                B, n1, n3, nleaf, float(_hp(self.hparams, "scale_factor")),
-                float(_hp(self.hparams, "match_threshold")), self.precision,
-                m0.data_ptr(), m1.data_ptr(), ms0.data_ptr(), ms1.data_ptr(), conf.data_ptr(),
-                ws.data_ptr(), ws_bytes, _lib.stream_ptr(dev))
-            _lib.check(rc, "onepose_match")
+                args.update(desc3d=d3, desc3d_bstride=s3, leaves=db, leaves_bstride=sl)
+                # (an older A/B build named by ONEPOSE_LIB has only the fp32 entry point, which
+                # would read fp16 descriptors as fp32)
+                if hasattr(lib, "onepose_match_dt"):
+                    _lib.run("onepose_match_dt", desc_dtype=dt, **args)
+                elif dt == _lib.DT_F16:
+                    raise _lib.OnePoseError("this libonepose_hip build (ABI < 4) has no fp16 "
+                                            "descriptor entry point (onepose_match_dt)")
+                else:
+                    _lib.run("onepose_match_ex", **args)
         pred = {"matches0": m0[0], "matches1": m1[0],
                 "matching_scores0": ms0[0], "matching_scores1": ms1[0]}
         return pred, conf

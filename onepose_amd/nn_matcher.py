@@ -91,19 +91,18 @@ def nearest_neighbour_match(desc0, desc1, ratio=None, distance=None, mutual=True
     dtype = torch.float16 if half else torch.float32
     d0, d0s = _operand(desc0, B, d, dtype)
     d1, d1s = _operand(desc1, B, d, dtype)
-    lib = _lib.load()
     with torch.cuda.device(dev):
         ws = _workspace(dev, B, n0, n1) if workspace is None else workspace
         m0 = torch.empty(B, n0, dtype=torch.int64, device=dev)
         m1 = torch.empty(B, n1, dtype=torch.int64, device=dev)
         s0 = torch.empty(B, n0, dtype=torch.float32, device=dev)
         s1 = torch.empty(B, n1, dtype=torch.float32, device=dev)
-        rc = lib.onepose_nn_match(d0.data_ptr(), d0s, d1.data_ptr(), d1s,
-                                  _lib.DT_F16 if half else _lib.DT_F32, B, d, n0, n1,
-                                  ratio, distance, int(bool(mutual)),
-                                  m0.data_ptr(), m1.data_ptr(), s0.data_ptr(), s1.data_ptr(),
-                                  ws.data_ptr(), ws.numel(), _lib.stream_ptr(dev))
-        _lib.check(rc, "onepose_nn_match")
+        _lib.run("onepose_nn_match", desc0=d0, desc0_bstride=d0s, desc1=d1, desc1_bstride=d1s,
+                 desc_dtype=_lib.DT_F16 if half else _lib.DT_F32, batch=B, d=d, n0=n0, n1=n1,
+                 ratio_threshold=ratio, distance_threshold=distance,
+                 do_mutual_check=int(bool(mutual)), matches0=m0, matches1=m1, mscores0=s0,
+                 mscores1=s1, workspace=ws, workspace_bytes=ws.numel(),
+                 stream=_lib.stream_ptr(dev))
     return m0, m1, s0, s1
 
 

@@ -140,7 +140,6 @@ def _i32(n, dev):
 
 def filter_points_device(xyz, track_len, min_track, corners, dev):
     """onepose_filter_points -> (xyz_out float32 [m, 3], index int32 [m]) on the device."""
-    lib = _lib.load()
     xyz = torch.as_tensor(xyz, dtype=torch.float64).to(dev).contiguous()
     n = xyz.shape[0]
     tl = None
@@ -148,10 +147,9 @@ def filter_points_device(xyz, track_len, min_track, corners, dev):
         tl = torch.as_tensor(np.minimum(np.asarray(track_len), 2**31 - 1).astype(np.int32)).to(dev)
     cn = None if corners is None else torch.as_tensor(corners, dtype=torch.float64).to(dev).contiguous()
     out, idx, cnt = torch.empty(n, 3, dtype=torch.float32, device=dev), _i32(n, dev), _i32(1, dev)
-    _lib.check(lib.onepose_filter_points(xyz.data_ptr(), _lib.ptr(tl), n,
-                                         int(min(int(min_track), 2**31 - 1)), _lib.ptr(cn),
-                                         out.data_ptr(), idx.data_ptr(), cnt.data_ptr(),
-                                         _lib.stream_ptr(dev)), "filter_points")
+    _lib.run("onepose_filter_points", xyz=xyz, track_len=tl, n=n,
+             min_track=int(min(int(min_track), 2**31 - 1)), corners=cn, xyz_out=out,
+             index_out=idx, count=cnt, stream=_lib.stream_ptr(dev))
     m = int(cnt.item())
     return out[:m], idx[:m]
 
@@ -167,15 +165,14 @@ def _xyz_dtype(xyz):
 def radius_neighbours_device(xyz, thr, capacity=None):
     """onepose_radius_neighbours -> (row_start int32 [n + 1], cols int32 [total]); the list is
     sized by a second call when the first capacity (2 n + 1024 by default) is too small."""
-    lib = _lib.load()
     dev, n, dt = xyz.device, xyz.shape[0], _xyz_dtype(xyz)
     rs, info = _i32(n + 1, dev), torch.empty(2, dtype=torch.int64, device=dev)
     cap = int(2 * n + 1024 if capacity is None else capacity)
     for _ in range(2):
         cols = _i32(max(cap, 1), dev)
-        _lib.check(lib.onepose_radius_neighbours(xyz.data_ptr(), dt, n, float(thr), rs.data_ptr(),
-                                                 cols.data_ptr(), cap, info.data_ptr(),
-                                                 _lib.stream_ptr(dev)), "radius_neighbours")
+        _lib.run("onepose_radius_neighbours", xyz=xyz, xyz_dtype=dt, n=n, thr=float(thr),
+                 row_start=rs, cols=cols, cols_capacity=cap, info=info,
+                 stream=_lib.stream_ptr(dev))
         total, status = (int(v) for v in info.tolist())
         if status == 0:
             return rs, cols[:total]
@@ -187,14 +184,12 @@ def radius_neighbours_device(xyz, thr, capacity=None):
 
 def merge_greedy_device(xyz, row_start, cols):
     """onepose_merge_greedy -> (cluster_of [n], member_start [m + 1], members, mean float64 [m, 3])."""
-    lib = _lib.load()
     dev, n = xyz.device, xyz.shape[0]
     cof, ms, mem, info = _i32(n, dev), _i32(n + 1, dev), _i32(n, dev), _i32(2, dev)
     mean = torch.empty(n, 3, dtype=torch.float64, device=dev)
-    _lib.check(lib.onepose_merge_greedy(xyz.data_ptr(), _xyz_dtype(xyz), n, row_start.data_ptr(),
-                                        cols.data_ptr(), cof.data_ptr(), ms.data_ptr(),
-                                        mem.data_ptr(), mean.data_ptr(), info.data_ptr(),
-                                        _lib.stream_ptr(dev)), "merge_greedy")
+    _lib.run("onepose_merge_greedy", xyz=xyz, xyz_dtype=_xyz_dtype(xyz), n=n, row_start=row_start,
+             cols=cols, cluster_of=cof, member_start=ms, members=mem, mean=mean, info=info,
+             stream=_lib.stream_ptr(dev))
     m, status = info.tolist()
     if status != 0:
         raise _lib.OnePoseError("merge_greedy: row_start / cols is not a CSR over these points")
@@ -205,17 +200,16 @@ def merge_greedy_device(xyz, row_start, cols):
 def lift_descriptors_device(bank, block_offset, block_cols, obs_block, obs_feat, seg_len, dim):
     """onepose_lift_descriptors on device tensors -> (seg_start int32 [n3 + 1], collected float64
     [dim, n_obs], mean64 [dim, n3], mean32 [dim, n3])."""
-    lib = _lib.load()
     dev, n_obs, n3 = bank.device, obs_block.shape[0], seg_len.shape[0]
     ss, info = _i32(n3 + 1, dev), _i32(2, dev)
     collected = torch.empty(dim, n_obs, dtype=torch.float64, device=dev)
     m64 = torch.empty(dim, n3, dtype=torch.float64, device=dev)
     m32 = torch.empty(dim, n3, dtype=torch.float32, device=dev)
-    _lib.check(lib.onepose_lift_descriptors(
-        bank.data_ptr(), bank.numel(), block_offset.data_ptr(), block_cols.data_ptr(),
-        block_cols.shape[0], obs_block.data_ptr(), obs_feat.data_ptr(), n_obs, seg_len.data_ptr(),
-        n3, dim, ss.data_ptr(), collected.data_ptr(), m64.data_ptr(), m32.data_ptr(),
-        info.data_ptr(), _lib.stream_ptr(dev)), "lift_descriptors")
+    _lib.run("onepose_lift_descriptors", bank=bank, bank_numel=bank.numel(),
+             block_offset=block_offset, block_cols=block_cols, n_blocks=block_cols.shape[0],
+             obs_block=obs_block, obs_feat=obs_feat, n_obs=n_obs, seg_len=seg_len, n3=n3, dim=dim,
+             seg_start=ss, collected=collected, mean64=m64, mean32=m32, info=info,
+             stream=_lib.stream_ptr(dev))
     status, where = info.tolist()
     if status != 0:
         raise _lib.OnePoseError(f"lift_descriptors: {LIFT_STATUS.get(status, status)} (index {where})")
@@ -224,14 +218,12 @@ def lift_descriptors_device(bank, block_offset, block_cols, obs_block, obs_feat,
 
 def gather_leaves_device(collected, cols):
     """onepose_gather_leaves -> float32 [dim, len(cols)]; ``cols`` int64, dustbin = n_obs."""
-    lib = _lib.load()
     dev = collected.device
     dim, n_obs = collected.shape
     cols = torch.as_tensor(cols, dtype=torch.int64).to(dev).contiguous()
     out = torch.empty(dim, cols.shape[0], dtype=torch.float32, device=dev)
-    _lib.check(lib.onepose_gather_leaves(collected.data_ptr(), n_obs, dim, cols.data_ptr(),
-                                         cols.shape[0], out.data_ptr(), _lib.stream_ptr(dev)),
-               "gather_leaves")
+    _lib.run("onepose_gather_leaves", collected=collected, n_obs=n_obs, dim=dim, cols=cols,
+             n_cols=cols.shape[0], out=out, stream=_lib.stream_ptr(dev))
     return out
 
 

@@ -42,6 +42,7 @@ import torch
 
 from . import _lib
 from .matcher import GATsSuperGlue
+from .prepared import PreparedObject
 
 
 class _Slot:
@@ -124,31 +125,17 @@ class FramePipeline:
         self.leaves = as_desc(leaves)
         self.L = self.leaves.shape[1] // self.n3
         assert self.L * self.n3 == self.leaves.shape[1] and self.kp3.shape[0] == self.n3
-        # the object's leaves, transposed once to the point-major layout the GAT layers read
-        self.leaves_pm = torch.empty(self.n3 * self.L * 256, **f32)
-        _lib.check(self.lib.onepose_prepare_leaves_dt(
-            self.leaves.data_ptr(), self.desc_dt, 0, 1, self.n3, self.L, self.leaves_pm.data_ptr(),
-            _lib.stream_ptr(dev)), "prepare_leaves")
-        # the object-only prefix of the forward (GAT 0 + the 3D half of self-attention 1) and,
-        # with gat_tables, the GAT prefix tables, computed once: every frame starts from it
+        # the object's leaves, transposed once to the point-major layout the GAT layers read, and
+        # the object-only prefix of the forward (GAT 0 + the 3D half of self-attention 1) with,
+        # for gat_tables, the GAT prefix tables, computed once: every frame starts from it
         # (onepose_match_cached; bit-identical to the uncached forward without the tables,
         # equal within rounding with them)
-        self.object_cache = None
         self.object_flags = _lib.OBJ_GAT_TABLES if gat_tables else 0
-        if object_cache:
-            nbytes = _lib.object_cache_bytes(self.lib, self.n3, self.L, self.object_flags,
-                                             self.precision)
-            self.object_cache = torch.empty(nbytes // 4, **f32)
-            wsb = self.lib.onepose_object_prepare_workspace_bytes(self.n3, self.L)
-            ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
-            _lib.check(self.lib.onepose_object_prepare_dt(
-                self.weights.data_ptr(), self.desc3d.data_ptr(), self.desc_dt,
-                self.leaves_pm.data_ptr(),
-                self.n3, self.L, self.precision, self.object_flags, self.object_cache.data_ptr(),
-                ws.data_ptr(), wsb,
-                _lib.stream_ptr(dev)), "object_prepare")
+        self.object = PreparedObject(self.weights, self.desc3d, self.leaves, self.precision,
+                                     self.object_flags, cache=object_cache)
+        self.leaves_pm, self.object_cache = self.object.leaves_pm, self.object.cache
+        if object_cache:   # the pipeline's streams are its own: they start behind the prepare
             torch.cuda.current_stream(dev).synchronize()
-            del ws
         B = self.B
         # per-frame inputs (filled by the caller)
         self.desc2d = torch.zeros(B, 256, n1, **fdesc)
@@ -164,16 +151,6 @@ class FramePipeline:
         self.image_hw = tuple(image_hw) if detector is not None else None
         self.slots = [_Slot(B, n1, self.n3, dev, with_conf, self.lib, self.L, self.iters,
                             self.image_hw, self.precision) for _ in range(max(1, slots))]
-
-    def __del__(self):
-        # drop the library's record of this object cache before its memory goes back to the
-        # allocator (onepose_object_release; a later cache at the address is prepared anew)
-        cache = self.__dict__.get("object_cache")
-        if cache is not None:
-            try:
-                self.lib.onepose_object_release(cache.data_ptr())
-            except Exception:
-                pass
 
     def __getattr__(self, name):
         # slot-0 outputs as attributes (pipe.pose, pipe.matches0, ...) for the common case
@@ -242,12 +219,14 @@ class FramePipeline:
         c = self.detector.config
         h, w = self.image_hw
         from .superpoint import reference_align_corners
-        _lib.check(self.lib.onepose_superpoint(
-            self.det_weights.data_ptr(), o.image.data_ptr(), self.B, h, w, int(c["nms_radius"]),
-            float(c["keypoint_threshold"]), int(c["remove_borders"]), self.n1,
-            int(reference_align_corners()), o.kpts2d.data_ptr(), o.det_scores.data_ptr(),
-            o.desc2d.data_ptr(), o.det_counts.data_ptr(), 0, 0, o.ws_det.data_ptr(),
-            o.ws_det_bytes, _lib.stream_ptr(self.device)), "onepose_superpoint")
+        _lib.run("onepose_superpoint", packed=self.det_weights, image=o.image, batch=self.B, h=h,
+                 w=w, nms_radius=int(c["nms_radius"]),
+                 keypoint_threshold=float(c["keypoint_threshold"]),
+                 remove_borders=int(c["remove_borders"]), max_keypoints=self.n1,
+                 align_corners=int(reference_align_corners()), keypoints=o.kpts2d,
+                 scores=o.det_scores, descriptors=o.desc2d, counts=o.det_counts, score_map=None,
+                 dense_desc=None, workspace=o.ws_det, workspace_bytes=o.ws_det_bytes,
+                 stream=_lib.stream_ptr(self.device))
 
     def enqueue_front(self, slot: int = 0, frame=None):
         """The stage that runs on a match stream: [detector ->] matcher (on frame-bank entry
@@ -272,23 +251,19 @@ class FramePipeline:
         if stages is None:
             self._primed = False   # the slot's staged input (if any) is overwritten
             stages = (_lib.STAGE_INPUTS, _lib.STAGE_WINNERS)
+        args = dict(packed_weights=self.weights, desc2d=desc2d, desc2d_bstride=256 * self.n1,
+                    leaves_prepared=self.leaves_pm, prepared_bstride=0, batch=self.B, n1=self.n1,
+                    n3=self.n3, num_leaf=self.L, scale_factor=self.scale_factor,
+                    match_threshold=self.threshold, precision=self.precision,
+                    matches0=o.matches0, matches1=o.matches1, mscores0=o.mscores0,
+                    mscores1=o.mscores1, conf=o._conf, workspace=o.ws_match,
+                    workspace_bytes=o.ws_match_bytes, stream=s)
         if self.object_cache is not None:
-            _lib.check(self.lib.onepose_match_cached_stages(
-                self.weights.data_ptr(), desc2d.data_ptr(), self.desc_dt, 256 * self.n1,
-                self.object_cache.data_ptr(), self.leaves_pm.data_ptr(), 0,
-                self.B, self.n1, self.n3, self.L, self.scale_factor, self.threshold,
-                self.precision, self.object_flags, o.matches0.data_ptr(), o.matches1.data_ptr(),
-                o.mscores0.data_ptr(), o.mscores1.data_ptr(), _lib.ptr(o._conf),
-                o.ws_match.data_ptr(), o.ws_match_bytes, stages[0], stages[1], s),
-                "onepose_match_cached")
-            return
-        _lib.check(self.lib.onepose_match_prepared_ex(
-            self.weights.data_ptr(), desc2d.data_ptr(), 256 * self.n1,
-            self.desc3d.data_ptr(), 0, self.leaves_pm.data_ptr(), 0,
-            self.B, self.n1, self.n3, self.L, self.scale_factor, self.threshold, self.precision,
-            o.matches0.data_ptr(), o.matches1.data_ptr(), o.mscores0.data_ptr(),
-            o.mscores1.data_ptr(), _lib.ptr(o._conf), o.ws_match.data_ptr(),
-            o.ws_match_bytes, s), "onepose_match_prepared")
+            _lib.run("onepose_match_cached_stages", desc_dtype=self.desc_dt,
+                     object_cache=self.object_cache, object_flags=self.object_flags,
+                     first_stage=stages[0], last_stage=stages[1], **args)
+        else:
+            _lib.run("onepose_match_prepared_ex", desc3d=self.desc3d, desc3d_bstride=0, **args)
 
     fused_pose = True   # enqueue_pose's default: onepose_pose_stage (two launches)
 
@@ -300,7 +275,6 @@ class FramePipeline:
         fused = self.fused_pose if fused is None else fused
         o = self.slots[slot]
         s = _lib.stream_ptr(self.device)
-        lib = self.lib
         _, kpts2d = self._inputs(o, frame)
         if frame is not None:
             K, pose_gt = self.bank["K"][frame], self.bank["pose_gt"][frame]
@@ -309,30 +283,24 @@ class FramePipeline:
             K, pose_gt = self.K, self.pose_gt
             r = {"pose": o.pose, "R_err": o.R_err, "t_err": o.t_err, "cmd": o.cmd,
                  "n_inliers": o.n_inliers, "status": o.status}
+        select = dict(matches0=o.matches0, kpts2d=kpts2d, kpts2d_bstride=self.n1 * 2,
+                      kpts3d=self.kp3, kpts3d_bstride=0, batch=self.B, n1=self.n1, n3=self.n3,
+                      pts2d=o.pts2d, pts3d=o.pts3d, counts=o.counts, stream=s)
+        solve = dict(K=K, K_bstride=9, scale=self.scale, reproj_error=self.reproj,
+                     max_iters=self.iters, confidence=self.conf_level, pose34=r["pose"],
+                     inlier_mask=o.inlier_mask, n_inliers=r["n_inliers"], status=r["status"],
+                     workspace=o.ws_pnp, workspace_bytes=o.ws_pnp_bytes)
+        errors = dict(pose_gt=pose_gt, gt_bstride=12, R_err_deg=r["R_err"], t_err_cm=r["t_err"],
+                      cmd=r["cmd"])
         if fused:
-            _lib.check(lib.onepose_pose_stage(
-                o.matches0.data_ptr(), kpts2d.data_ptr(), self.n1 * 2, self.kp3.data_ptr(), 0,
-                self.B, self.n1, self.n3, self.scale, K.data_ptr(), 9, self.reproj,
-                self.iters, self.conf_level, pose_gt.data_ptr(), 12, o.pts2d.data_ptr(),
-                o.pts3d.data_ptr(), o.counts.data_ptr(), r["pose"].data_ptr(),
-                o.inlier_mask.data_ptr(), r["n_inliers"].data_ptr(), r["status"].data_ptr(),
-                r["R_err"].data_ptr(), r["t_err"].data_ptr(), r["cmd"].data_ptr(),
-                o.ws_pnp.data_ptr(), o.ws_pnp_bytes, s), "pose_stage")
+            _lib.run("onepose_pose_stage", **select, **solve, **errors)
             return
         if frame is not None:
             raise ValueError("frame-bank entries run the fused pose stage")
-        _lib.check(lib.onepose_select_correspondences(
-            o.matches0.data_ptr(), kpts2d.data_ptr(), self.n1 * 2, self.kp3.data_ptr(), 0,
-            self.B, self.n1, self.n3, self.scale, o.pts2d.data_ptr(), o.pts3d.data_ptr(),
-            o.counts.data_ptr(), s), "select_correspondences")
-        _lib.check(lib.onepose_pnp_ransac(
-            o.pts2d.data_ptr(), o.pts3d.data_ptr(), o.counts.data_ptr(), self.n1,
-            self.K.data_ptr(), 9, self.B, self.scale, self.reproj, self.iters, self.conf_level,
-            o.pose.data_ptr(), o.inlier_mask.data_ptr(), o.n_inliers.data_ptr(),
-            o.status.data_ptr(), o.ws_pnp.data_ptr(), o.ws_pnp_bytes, s), "pnp_ransac")
-        _lib.check(lib.onepose_pose_errors(
-            o.pose.data_ptr(), self.pose_gt.data_ptr(), 12, self.B, o.R_err.data_ptr(),
-            o.t_err.data_ptr(), o.cmd.data_ptr(), s), "pose_errors")
+        _lib.run("onepose_select_correspondences", scale3d=self.scale, **select)
+        _lib.run("onepose_pnp_ransac", pts2d=o.pts2d, pts3d=o.pts3d, counts=o.counts,
+                 max_points=self.n1, batch=self.B, stream=s, **solve)
+        _lib.run("onepose_pose_errors", pose_pred=o.pose, batch=self.B, stream=s, **errors)
 
     def enqueue(self, slot: int = 0):
         self.enqueue_front(slot)

@@ -30,7 +30,6 @@ def select_correspondences(matches0, kpts2d, kpts3d, scale=1.0):
     ``kpts2d [B,N1,2]``, ``kpts3d [B,N3,3]`` (or ``[N3,3]`` shared) -> compacted
     ``pts2d [B,N1,2]``, ``pts3d [B,N1,3]`` float32 (3D scaled by ``scale`` in float64 then
     rounded to float32, as solvePnPRansac sees them) and ``counts [B]`` int32."""
-    lib = _lib.load()
     if kpts3d.dim() == 2:
         kpts3d = kpts3d[None]
     B, n1 = matches0.shape
@@ -47,10 +46,9 @@ def select_correspondences(matches0, kpts2d, kpts3d, scale=1.0):
     p2 = torch.empty(B, n1, 2, dtype=torch.float32, device=dev)
     p3 = torch.empty(B, n1, 3, dtype=torch.float32, device=dev)
     counts = torch.empty(B, dtype=torch.int32, device=dev)
-    _lib.check(lib.onepose_select_correspondences(
-        matches0.contiguous().data_ptr(), kp2.data_ptr(), n1 * 2, kp3.data_ptr(), kp3_bs, B, n1, n3,
-        float(scale), p2.data_ptr(), p3.data_ptr(), counts.data_ptr(), _lib.stream_ptr(dev)),
-        "select_correspondences")
+    _lib.run("onepose_select_correspondences", matches0=matches0.contiguous(), kpts2d=kp2,
+             kpts2d_bstride=n1 * 2, kpts3d=kp3, kpts3d_bstride=kp3_bs, batch=B, n1=n1, n3=n3,
+             scale3d=float(scale), pts2d=p2, pts3d=p3, counts=counts, stream=_lib.stream_ptr(dev))
     return p2, p3, counts
 
 
@@ -73,18 +71,18 @@ def ransac_pnp_batch(pts2d, pts3d, counts, K, scale=1.0, reprojection_error=5.0,
     ws_bytes = lib.onepose_pnp_workspace_bytes(B, M, int(iterations_count))
     if workspace is None or workspace.numel() < ws_bytes:
         workspace = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
-    _lib.check(lib.onepose_pnp_ransac(
-        pts2d.contiguous().data_ptr(), pts3d.contiguous().data_ptr(), counts.data_ptr(), M,
-        K.data_ptr(), k_bs, B, float(scale), float(reprojection_error), int(iterations_count),
-        float(confidence), pose.data_ptr(), mask.data_ptr(), n_in.data_ptr(), status.data_ptr(),
-        workspace.data_ptr(), ws_bytes, _lib.stream_ptr(dev)), "pnp_ransac")
+    _lib.run("onepose_pnp_ransac", pts2d=pts2d.contiguous(), pts3d=pts3d.contiguous(),
+             counts=counts, max_points=M, K=K, K_bstride=k_bs, batch=B, scale=float(scale),
+             reproj_error=float(reprojection_error), max_iters=int(iterations_count),
+             confidence=float(confidence), pose34=pose, inlier_mask=mask, n_inliers=n_in,
+             status=status, workspace=workspace, workspace_bytes=ws_bytes,
+             stream=_lib.stream_ptr(dev))
     return pose, mask, n_in, status
 
 
 def pose_errors(pose_pred, pose_gt):
     """Device cm/deg errors: ``pose_pred [B,3,4]``, ``pose_gt [B,3,4]`` or ``[3,4]`` float64
     -> ``(R_err_deg [B], t_err_cm [B], cmd [B,3] uint8 for 1/3/5 cm-deg)``."""
-    lib = _lib.load()
     dev = pose_pred.device
     B = pose_pred.shape[0]
     gt = torch.as_tensor(pose_gt, dtype=torch.float64, device=dev)
@@ -95,9 +93,8 @@ def pose_errors(pose_pred, pose_gt):
     r = torch.empty(B, dtype=torch.float64, device=dev)
     t = torch.empty(B, dtype=torch.float64, device=dev)
     cmd = torch.empty(B, 3, dtype=torch.uint8, device=dev)
-    _lib.check(lib.onepose_pose_errors(pose_pred.contiguous().data_ptr(), gt.data_ptr(), gt_bs, B,
-                                       r.data_ptr(), t.data_ptr(), cmd.data_ptr(),
-                                       _lib.stream_ptr(dev)), "pose_errors")
+    _lib.run("onepose_pose_errors", pose_pred=pose_pred.contiguous(), pose_gt=gt, gt_bstride=gt_bs,
+             batch=B, R_err_deg=r, t_err_cm=t, cmd=cmd, stream=_lib.stream_ptr(dev))
     return r, t, cmd
 
 

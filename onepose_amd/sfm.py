@@ -263,17 +263,16 @@ def write_model_binary(model, path):
 def track_components_device(edges, n_nodes, rounds=CC_ROUNDS, max_calls=CC_MAX_CALLS):
     """onepose_track_components until it reports convergence -> ``(labels int32 [n_nodes],
     status rows)``.  ``edges``: int32 ``[E, 2]`` on the device."""
-    lib = _lib.load()
     dev = edges.device
     edges = edges.contiguous()
     parent = torch.empty(n_nodes, dtype=torch.int32, device=dev)
     status = torch.empty(4, dtype=torch.int32, device=dev)
     rows = []
     for call in range(max_calls):
-        _lib.check(lib.onepose_track_components(
-            edges.data_ptr() if edges.shape[0] else None, edges.shape[0], n_nodes, rounds,
-            1 if call == 0 else 0, parent.data_ptr(), status.data_ptr(), _lib.stream_ptr(dev)),
-            "track_components")
+        _lib.run("onepose_track_components", edges=edges if edges.shape[0] else None,
+                 n_edges=edges.shape[0], n_nodes=n_nodes, rounds=rounds,
+                 init=1 if call == 0 else 0, parent=parent, status=status,
+                 stream=_lib.stream_ptr(dev))
         rows.append(status.tolist())
         if rows[-1][0] == 0:
             return parent, rows
@@ -338,7 +337,6 @@ def build_tracks(n_feats_per_image, edges, device=None):
 def tracks_triangulate_device(Rt, K4, track_start, obs_image, obs_xy, max_reproj, min_angle_deg):
     """onepose_tracks_triangulate on device tensors -> ``(xyz, err, reason, n_kept, obs_keep,
     status)`` tensors; nothing is synchronised."""
-    lib = _lib.load()
     dev = Rt.device
     n_tracks, n_obs = track_start.shape[0] - 1, obs_image.shape[0]
     xyz = torch.empty(n_tracks, 3, dtype=torch.float64, device=dev)
@@ -347,11 +345,11 @@ def tracks_triangulate_device(Rt, K4, track_start, obs_image, obs_xy, max_reproj
     n_kept = torch.empty(n_tracks, dtype=torch.int32, device=dev)
     obs_keep = torch.empty(n_obs, dtype=torch.uint8, device=dev)
     status = torch.empty(2, dtype=torch.int32, device=dev)
-    _lib.check(lib.onepose_tracks_triangulate(
-        Rt.data_ptr(), K4.data_ptr(), Rt.shape[0], track_start.data_ptr(), obs_image.data_ptr(),
-        obs_xy.data_ptr(), n_tracks, n_obs, float(max_reproj), float(min_angle_deg),
-        xyz.data_ptr(), err.data_ptr(), reason.data_ptr(), n_kept.data_ptr(), obs_keep.data_ptr(),
-        status.data_ptr(), _lib.stream_ptr(dev)), "tracks_triangulate")
+    _lib.run("onepose_tracks_triangulate", Rt=Rt, K4=K4, n_images=Rt.shape[0],
+             track_start=track_start, obs_image=obs_image, obs_xy=obs_xy, n_tracks=n_tracks,
+             n_obs=n_obs, max_reproj=float(max_reproj), min_angle_deg=float(min_angle_deg), xyz=xyz,
+             err=err, reason=reason, n_kept=n_kept, obs_keep=obs_keep, status=status,
+             stream=_lib.stream_ptr(dev))
     return xyz, err, reason, n_kept, obs_keep, status
 
 

@@ -23,6 +23,7 @@ import torch.distributed as dist
 
 from . import _lib
 from .matcher import GATsSuperGlue, _hp
+from .prepared import PreparedObject
 
 
 def shard_range(n3_total: int, world: int, rank: int):
@@ -56,17 +57,16 @@ class ShardedMatcher:
         s, c, L = self.start, self.count, self.L
         self.desc3d = d3[:, s:s + c].contiguous().to(self.dev)
         shard_leaves = lv[:, s * L:(s + c) * L].contiguous().to(self.dev)
-        self.leaves_pm = torch.empty(c * L * 256, **f32)
-        _lib.check(self.lib.onepose_prepare_leaves(shard_leaves.data_ptr(), 0, 1, c, L,
-                                                   self.leaves_pm.data_ptr(),
-                                                   _lib.stream_ptr(self.dev)), "prepare_leaves")
         self.weights = matcher.packed_weights(self.dev)
+        self.object = PreparedObject(self.weights, self.desc3d, shard_leaves, self.precision,
+                                     cache=False)
+        self.leaves_pm = self.object.leaves_pm
         xb = self.lib.onepose_match_sharded_xchg_bytes(self.B, self.n1, self.n3, self.world)
         self.xchg_bytes = xb
         self.send = torch.empty(xb, dtype=torch.uint8, device=self.dev)
         self.recv = torch.empty(self.world * xb, dtype=torch.uint8, device=self.dev)
-        wb = self.lib.onepose_match_sharded_workspace_bytes(self.B, self.n1, self.n3, self.world,
-                                                            self.rank, L, 0)
+        wb = _lib.call("onepose_match_sharded_workspace_bytes", batch=self.B, n1=self.n1,
+                       n3_total=self.n3, world=self.world, rank=self.rank, num_leaf=L, with_conf=0)
         self.ws_bytes = wb
         self.ws = torch.empty(wb, dtype=torch.uint8, device=self.dev)
         B = self.B
@@ -101,14 +101,17 @@ class ShardedMatcher:
         mscores0, mscores1), the whole frame's results on every rank."""
         d2 = desc2d.float().contiguous()
         assert tuple(d2.shape) == (self.B, 256, self.n1), tuple(d2.shape)
-        rc = self.lib.onepose_match_sharded(
-            self.weights.data_ptr(), d2.data_ptr(), 256 * self.n1, self.desc3d.data_ptr(), 0,
-            self.leaves_pm.data_ptr(), 0, self.B, self.n1, self.n3, self.L, self.world,
-            self.rank, self.scale_factor, self.threshold, self.precision,
-            self.send.data_ptr(), self.recv.data_ptr(), self.xchg_bytes, self._cb, None,
-            self.matches0.data_ptr(), self.matches1.data_ptr(), self.mscores0.data_ptr(),
-            self.mscores1.data_ptr(), None, self.ws.data_ptr(), self.ws_bytes,
-            _lib.stream_ptr(self.dev))
+        rc = _lib.call(
+            "onepose_match_sharded", packed_weights=self.weights, desc2d=d2,
+            desc2d_bstride=256 * self.n1, desc3d_shard=self.desc3d, desc3d_bstride=0,
+            leaves_shard_prepared=self.leaves_pm, prepared_bstride=0, batch=self.B, n1=self.n1,
+            n3_total=self.n3, num_leaf=self.L, world=self.world, rank=self.rank,
+            scale_factor=self.scale_factor, match_threshold=self.threshold,
+            precision=self.precision, xchg_send=self.send, xchg_recv=self.recv,
+            xchg_bytes=self.xchg_bytes, allgather=self._cb, user=None, matches0=self.matches0,
+            matches1=self.matches1, mscores0=self.mscores0, mscores1=self.mscores1,
+            conf_shard=None, workspace=self.ws, workspace_bytes=self.ws_bytes,
+            stream=_lib.stream_ptr(self.dev))
         if rc != 0 and self._error:
             raise RuntimeError(f"onepose_match_sharded: all-gather failed\n{self._error}")
         _lib.check(rc, "onepose_match_sharded")

@@ -190,7 +190,6 @@ class SuperGlue(nn.Module):
         s1, s1s = self._operand(data["scores1"], B, (n1,))
         h0, w0 = data["image0"].shape[-2:]
         h1, w1 = data["image1"].shape[-2:]
-        lib = _lib.load()
         with torch.cuda.device(dev):
             w = self.packed_weights(dev)
             ws = self._workspace(dev, B, n0, n1)
@@ -200,14 +199,15 @@ class SuperGlue(nn.Module):
             ms1 = torch.empty(B, n1, dtype=torch.float32, device=dev)
             la = (torch.empty(B, n0 + 1, n1 + 1, dtype=torch.float32, device=dev)
                   if return_log_assignment else None)
-            rc = lib.onepose_superglue_match(
-                w.data_ptr(), d0.data_ptr(), d0s, k0.data_ptr(), k0s, s0.data_ptr(), s0s,
-                d1.data_ptr(), d1s, k1.data_ptr(), k1s, s1.data_ptr(), s1s,
-                B, n0, n1, int(h0), int(w0), int(h1), int(w1),
-                int(self.config["sinkhorn_iterations"]), float(self.config["match_threshold"]),
-                PREC_FP32, m0.data_ptr(), m1.data_ptr(), ms0.data_ptr(), ms1.data_ptr(),
-                _lib.ptr(la), ws.data_ptr(), ws.numel(), _lib.stream_ptr(dev))
-            _lib.check(rc, "onepose_superglue_match")
+            _lib.run("onepose_superglue_match", packed_weights=w, desc0=d0, desc0_bstride=d0s,
+                     kpts0=k0, kpts0_bstride=k0s, scores0=s0, scores0_bstride=s0s, desc1=d1,
+                     desc1_bstride=d1s, kpts1=k1, kpts1_bstride=k1s, scores1=s1,
+                     scores1_bstride=s1s, batch=B, n0=n0, n1=n1, h0=int(h0), w0=int(w0),
+                     h1=int(h1), w1=int(w1),
+                     sinkhorn_iters=int(self.config["sinkhorn_iterations"]),
+                     match_threshold=float(self.config["match_threshold"]), precision=PREC_FP32,
+                     matches0=m0, matches1=m1, mscores0=ms0, mscores1=ms1, log_assignment=la,
+                     workspace=ws, workspace_bytes=ws.numel(), stream=_lib.stream_ptr(dev))
         out = {"matches0": m0, "matches1": m1, "matching_scores0": ms0, "matching_scores1": ms1}
         if return_log_assignment:
             out["log_assignment"] = la

@@ -47,15 +47,14 @@ def sample_descriptors(keypoints, descriptors, s: int = 8, align_corners=None):
         align_corners = reference_align_corners()
     if descriptors.device.type != "cuda":
         raise RuntimeError("onepose_amd.sample_descriptors runs on a ROCm GPU only")
-    lib = _lib.load()
     b, c, h, w = descriptors.shape
     n = keypoints.shape[1]
     kp = keypoints.float().contiguous()
     d = descriptors.float().contiguous()
     out = torch.empty(b, c, n, dtype=torch.float32, device=d.device)
-    _lib.check(lib.onepose_sample_descriptors(kp.data_ptr(), d.data_ptr(), b, n, c, h, w, int(s),
-                                              int(bool(align_corners)), out.data_ptr(),
-                                              _lib.stream_ptr(d.device)), "sample_descriptors")
+    _lib.run("onepose_sample_descriptors", keypoints=kp, dense=d, batch=b, n=n, c=c, h=h, w=w,
+             s=int(s), align_corners=int(bool(align_corners)), out=out,
+             stream=_lib.stream_ptr(d.device))
     return out
 
 
@@ -172,7 +171,6 @@ class SuperPoint:
         b, h, w = img.shape
         if h % 8 or w % 8:
             raise ValueError(f"image {h}x{w}: sides must be multiples of 8")
-        lib = _lib.load()
         k = self.capacity(h, w)
         dev = img.device
         out = {"keypoints": torch.empty(b, k, 2, device=dev),
@@ -185,13 +183,14 @@ class SuperPoint:
             out["dense"] = torch.empty(b, h // 8, w // 8, 256, device=dev)
         ws = self._workspace(b, h, w)
         c = self.config
-        _lib.check(lib.onepose_superpoint(
-            self.packed_weights().data_ptr(), img.data_ptr(), b, h, w, int(c["nms_radius"]),
-            float(c["keypoint_threshold"]), int(c["remove_borders"]), k,
-            int(reference_align_corners()), out["keypoints"].data_ptr(), out["scores"].data_ptr(),
-            out["descriptors"].data_ptr(), out["counts"].data_ptr(), _lib.ptr(out.get("score_map")),
-            _lib.ptr(out.get("dense")), ws.data_ptr(), ws.numel(), _lib.stream_ptr(dev)),
-            "superpoint")
+        _lib.run("onepose_superpoint", packed=self.packed_weights(), image=img, batch=b, h=h, w=w,
+                 nms_radius=int(c["nms_radius"]),
+                 keypoint_threshold=float(c["keypoint_threshold"]),
+                 remove_borders=int(c["remove_borders"]), max_keypoints=k,
+                 align_corners=int(reference_align_corners()), keypoints=out["keypoints"],
+                 scores=out["scores"], descriptors=out["descriptors"], counts=out["counts"],
+                 score_map=out.get("score_map"), dense_desc=out.get("dense"), workspace=ws,
+                 workspace_bytes=ws.numel(), stream=_lib.stream_ptr(dev))
         return out
 
     def forward(self, inp):
@@ -243,9 +242,8 @@ def run_layer(packed, layer: int, x):
     need = lib.onepose_superpoint_layer_out_floats(int(layer), h, w)
     if need and y[0].numel() != need:   # (0: a size the entry point refuses, with its message)
         raise _lib.OnePoseError("superpoint_layer: output size disagrees with the library")
-    _lib.check(lib.onepose_superpoint_layer(packed.data_ptr(), int(layer), x.data_ptr(), b, h, w,
-                                            y.data_ptr(), _lib.stream_ptr(x.device)),
-               "superpoint_layer")
+    _lib.run("onepose_superpoint_layer", packed=packed, layer=int(layer), x=x, batch=b, h=h, w=w,
+             y=y, stream=_lib.stream_ptr(x.device))
     return y
 
 
@@ -271,9 +269,9 @@ def detect_from_maps(score_map, dense_nhwc, nms_radius=4, keypoint_threshold=0.0
            "counts": torch.empty(b, dtype=torch.int32, device=dev)}
     nws = lib.onepose_superpoint_detect_workspace_bytes(b, h, w)
     ws = torch.empty(nws, dtype=torch.uint8, device=dev)
-    _lib.check(lib.onepose_superpoint_detect(
-        s.data_ptr(), d.data_ptr(), b, h, w, int(nms_radius), float(keypoint_threshold),
-        int(remove_borders), k, int(bool(align_corners)), out["keypoints"].data_ptr(),
-        out["scores"].data_ptr(), out["descriptors"].data_ptr(), out["counts"].data_ptr(),
-        ws.data_ptr(), nws, _lib.stream_ptr(dev)), "superpoint_detect")
+    _lib.run("onepose_superpoint_detect", score_map=s, dense_desc=d, batch=b, h=h, w=w,
+             nms_radius=int(nms_radius), keypoint_threshold=float(keypoint_threshold),
+             remove_borders=int(remove_borders), max_keypoints=k,
+             align_corners=int(bool(align_corners)), **out, workspace=ws, workspace_bytes=nws,
+             stream=_lib.stream_ptr(dev))
     return out

@@ -53,9 +53,9 @@ def build_index(ptIdx, camIdx, n_cams: int, n_points: int):
         raise ValueError(f"bundle_adjust: unsupported shape N={len(pt)}, C={n_cams}, P={n_points}")
     buf = np.zeros(nbytes, dtype=np.uint8)
     a, pa = ctypes.c_int(0), ctypes.c_int(0)
-    _lib.check(lib.onepose_ba_build_index(pt.ctypes.data, cam.ctypes.data, len(pt), n_cams,
-                                          n_points, buf.ctypes.data, nbytes, ctypes.byref(a),
-                                          ctypes.byref(pa)), "onepose_ba_build_index")
+    _lib.run("onepose_ba_build_index", ptIdx=pt.ctypes.data, camIdx=cam.ctypes.data, n_obs=len(pt),
+             n_cams=n_cams, n_points=n_points, index=buf.ctypes.data, index_bytes=nbytes,
+             n_active_cams=ctypes.byref(a), n_active_points=ctypes.byref(pa))
     return buf, int(a.value), int(pa.value)
 
 
@@ -102,12 +102,11 @@ def bundle_adjust(points, cam_pose, features, ptIdx, camIdx, numIterations=5,
         ix = torch.from_numpy(buf).to(dev)
         ws = torch.empty(lib.onepose_ba_workspace_bytes(N, A, Pa), dtype=torch.uint8, device=dev)
         info = torch.empty(INFO_DOUBLES, dtype=torch.float64, device=dev)
-        rc = lib.onepose_ba_solve(points.data_ptr(), cam_pose.data_ptr(), features.data_ptr(),
-                                  ptIdx.data_ptr(), camIdx.data_ptr(), ix.data_ptr(), N, C, P, A,
-                                  Pa, int(numIterations), int(numSuccessIterations),
-                                  float(initial_radius), info.data_ptr(), ws.data_ptr(),
-                                  ws.numel(), _lib.stream_ptr(dev))
-        _lib.check(rc, "onepose_ba_solve")
+        _lib.run("onepose_ba_solve", points=points, cam_pose=cam_pose, features=features,
+                 ptIdx=ptIdx, camIdx=camIdx, index=ix, n_obs=N, n_cams=C, n_points=P,
+                 n_active_cams=A, n_active_points=Pa, max_iters=int(numIterations),
+                 max_success=int(numSuccessIterations), initial_radius=float(initial_radius),
+                 info=info, workspace=ws, workspace_bytes=ws.numel(), stream=_lib.stream_ptr(dev))
     return info
 
 
@@ -185,7 +184,6 @@ def triangulate_points(P1, P2, pts1, pts2, rep_thr=20.0, z_max=0.15):
     n = pts1.shape[0]
     if pts2.shape[0] != n:
         raise ValueError("pts1 and pts2 differ in length")
-    lib = _lib.load()
     dev = pts1.device
     P1, P2 = P1.contiguous(), P2.contiguous()
     with torch.cuda.device(dev):
@@ -193,12 +191,9 @@ def triangulate_points(P1, P2, pts1, pts2, rep_thr=20.0, z_max=0.15):
         out = {"points": torch.empty(n, 3, **f64), "err1": torch.empty(n, **f64),
                "err2": torch.empty(n, **f64), "z": torch.empty(n, **f64),
                "keep": torch.empty(n, dtype=torch.uint8, device=dev)}
-        rc = lib.onepose_triangulate(P1.data_ptr(), P2.data_ptr(), pts1.data_ptr(),
-                                     pts2.data_ptr(), n, float(rep_thr), float(z_max),
-                                     out["points"].data_ptr(), out["err1"].data_ptr(),
-                                     out["err2"].data_ptr(), out["z"].data_ptr(),
-                                     out["keep"].data_ptr(), _lib.stream_ptr(dev))
-        _lib.check(rc, "onepose_triangulate")
+        _lib.run("onepose_triangulate", P1=P1, P2=P2, pts1=pts1, pts2=pts2, n=n,
+                 rep_thr=float(rep_thr), z_max=float(z_max), X=out["points"], err1=out["err1"],
+                 err2=out["err2"], z=out["z"], keep=out["keep"], stream=_lib.stream_ptr(dev))
     return out
 
 
@@ -290,10 +285,9 @@ def lk_pyramid_layout(h, w, win, max_level, level):
     """onepose_lk_pyramid_layout (a host function): (lh, lw, image offset, derivative offset)."""
     lh, lw = ctypes.c_int(0), ctypes.c_int(0)
     io, do = ctypes.c_int64(0), ctypes.c_int64(0)
-    _lib.check(_lib.load().onepose_lk_pyramid_layout(h, w, win, max_level, level,
-                                                     ctypes.byref(lh), ctypes.byref(lw),
-                                                     ctypes.byref(io), ctypes.byref(do)),
-               "onepose_lk_pyramid_layout")
+    _lib.run("onepose_lk_pyramid_layout", h=h, w=w, win=win, max_level=max_level, level=level,
+             lh=ctypes.byref(lh), lw=ctypes.byref(lw), image_offset=ctypes.byref(io),
+             deriv_offset=ctypes.byref(do))
     return int(lh.value), int(lw.value), int(io.value), int(do.value)
 
 
@@ -317,10 +311,9 @@ def build_lk_pyramid(image_u8, win=15, max_level=2, with_deriv=True):
     dev = img.device
     with torch.cuda.device(dev):
         blob = torch.empty(B, nbytes, dtype=torch.uint8, device=dev)
-        _lib.check(lib.onepose_lk_build_pyramid(img.data_ptr(), h * w, B, h, w, int(win),
-                                                int(max_level), int(bool(with_deriv)),
-                                                blob.data_ptr(), _lib.stream_ptr(dev)),
-                   "onepose_lk_build_pyramid")
+        _lib.run("onepose_lk_build_pyramid", image=img, image_bstride=h * w, batch=B, h=h, w=w,
+                 win=int(win), max_level=int(max_level), with_deriv=int(bool(with_deriv)),
+                 pyramids=blob, stream=_lib.stream_ptr(dev))
     return LKPyramid(blob, h, w, int(win), int(max_level), with_deriv)
 
 
@@ -353,7 +346,6 @@ def lk_track(prev_pyr, next_pyr, prev_pts, counts=None, max_count=10, epsilon=0.
     prev_pts = prev_pts.contiguous()
     shared_pts = prev_pts.dim() == 2 or prev_pts.shape[0] == 1
     dev = prev_pts.device
-    lib = _lib.load()
     with torch.cuda.device(dev):
         if counts is None:
             counts = torch.full((B,), n, dtype=torch.int32, device=dev)
@@ -363,14 +355,14 @@ def lk_track(prev_pyr, next_pyr, prev_pts, counts=None, max_count=10, epsilon=0.
             _need_gpu(counts)
             next_pts = prev_pts.reshape(-1, n, 2).expand(B, n, 2).clone()
             status = torch.zeros(B, n, dtype=torch.uint8, device=dev)
-        rc = lib.onepose_lk_track(prev_pyr.blob.data_ptr(),
-                                  0 if prev_pyr.batch == 1 else prev_pyr.blob.shape[1],
-                                  next_pyr.blob.data_ptr(), prev_pts.data_ptr(),
-                                  0 if shared_pts else 2 * n, counts.data_ptr(), B, n,
-                                  prev_pyr.h, prev_pyr.w, prev_pyr.win, prev_pyr.max_level,
-                                  int(max_count), float(epsilon), float(min_eig_threshold),
-                                  next_pts.data_ptr(), status.data_ptr(), _lib.stream_ptr(dev))
-        _lib.check(rc, "onepose_lk_track")
+        _lib.run("onepose_lk_track", prev_pyr=prev_pyr.blob,
+                 prev_pyr_bstride=0 if prev_pyr.batch == 1 else prev_pyr.blob.shape[1],
+                 next_pyr=next_pyr.blob, prev_pts=prev_pts,
+                 prev_pts_bstride=0 if shared_pts else 2 * n, counts=counts, batch=B,
+                 max_points=n, h=prev_pyr.h, w=prev_pyr.w, win=prev_pyr.win,
+                 max_level=prev_pyr.max_level, max_count=int(max_count), epsilon=float(epsilon),
+                 min_eig_threshold=float(min_eig_threshold), next_pts=next_pts, status=status,
+                 stream=_lib.stream_ptr(dev))
     return next_pts, status
 
 
