@@ -1093,4 +1093,8 @@ const char* onepose_profile_kind_name(int kind);
 #ifdef __cplusplus
 }
 #endif
+
+/* Families added after ABI 9 keep their declarations and contract in a header of their own. */
+#include "onepose_two_view.h"   /* two-view verification: batched F-matrix RANSAC */
+
 #endif /* ONEPOSE_HIP_H */

@@ -20,6 +20,9 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # ONEPOSE_LIB: an alternative in-tree build of the same library (A/B measurement, tools/ab.sh)
 LIB_PATH = os.environ.get("ONEPOSE_LIB") or os.path.join(_HERE, "libonepose_hip.so")
 HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "onepose_hip.h")
+# Families added after ABI 9 declare themselves in headers of their own, which onepose_hip.h
+# includes: SIGNATURES / PROTOTYPES stay the ABI-9 header's table, FAMILY_SIGNATURES holds theirs.
+FAMILY_HEADERS = ("onepose_two_view.h",)
 
 c_int, c_int64, c_size_t, c_float, c_double = (ctypes.c_int, ctypes.c_int64, ctypes.c_size_t,
                                                ctypes.c_float, ctypes.c_double)
@@ -106,12 +109,13 @@ def parse_header(text):
     return signatures, enums
 
 
-def _read_header():
+def _read_header(path=None):
+    path = path or HEADER_PATH
     try:
-        with open(HEADER_PATH) as f:
+        with open(path) as f:
             return f.read()
     except OSError as e:
-        raise OnePoseError(f"{HEADER_PATH} is missing ({e.strerror}): onepose_amd reads the "
+        raise OnePoseError(f"{path} is missing ({e.strerror}): onepose_amd reads the "
                            "library's signatures from it (in-tree layout)") from None
 
 
@@ -119,11 +123,20 @@ def _read_header():
 SIGNATURES, ENUMS = parse_header(_read_header())
 # name -> (restype, [argtypes])
 PROTOTYPES = {name: (res, [t for _, t in params]) for name, (res, params) in SIGNATURES.items()}
+# the family headers' declarations, same shape as SIGNATURES / PROTOTYPES
+FAMILY_SIGNATURES = {}
+for _h in FAMILY_HEADERS:
+    _sigs, _ = parse_header(_read_header(os.path.join(os.path.dirname(HEADER_PATH), _h)))
+    if set(_sigs) & (set(SIGNATURES) | set(FAMILY_SIGNATURES)):
+        raise OnePoseError(f"{_h}: declares a function that another header declares")
+    FAMILY_SIGNATURES.update(_sigs)
+FAMILY_PROTOTYPES = {name: (res, [t for _, t in params])
+                     for name, (res, params) in FAMILY_SIGNATURES.items()}
 # name -> (keyword names in order, indices of the pointer parameters); a parameter named like
 # a Python keyword takes a trailing underscore (onepose_affine_partial_ransac's from_)
 _ORDER = {name: (tuple(n + "_" * keyword.iskeyword(n) for n, _ in params),
                  tuple(i for i, (_, t) in enumerate(params) if t is c_void_p))
-          for name, (_, params) in SIGNATURES.items()}
+          for name, (_, params) in {**SIGNATURES, **FAMILY_SIGNATURES}.items()}
 
 _lib = None
 
@@ -140,7 +153,7 @@ def load():
         # A/B measurement only: an older build named by ONEPOSE_LIB may predate the newest
         # entry points (ABI >= 3); callers fall back where one is missing (size_query)
         ab = bool(os.environ.get("ONEPOSE_LIB"))
-        for name, (res, args) in PROTOTYPES.items():
+        for name, (res, args) in {**PROTOTYPES, **FAMILY_PROTOTYPES}.items():
             if ab and not hasattr(lib, name):
                 continue
             fn = getattr(lib, name)
@@ -162,7 +175,7 @@ def call(name, **args):
     try:
         names, pointers = _ORDER[name]
     except KeyError:
-        raise TypeError(f"{name} is not declared in onepose_hip.h") from None
+        raise TypeError(f"{name} is not declared in onepose_hip.h or a family header") from None
     try:
         vals = [args[n] for n in names]
     except KeyError as e:

@@ -12,6 +12,13 @@ The reference's ``sfm_core`` (``run.py:140-193``) after feature extraction, stag
 * ``rotmat2qvec`` / ``empty_model`` / ``write_model_binary``
                               -- ``src/sfm/generate_empty.py:31-90`` and COLMAP's binary model
                                  format, byte for byte what the reference's ``write_model`` writes
+* ``fundamental_from_poses`` / ``verify_matches``
+                              -- the step the reference leaves to COLMAP's ``matches_importer``
+                                 (``triangulation.py:18-35``), between ``import_matches`` and the
+                                 triangulator.  **This project's own**: per pair a fundamental
+                                 matrix by RANSAC over the normalised 8-point algorithm (or the F of
+                                 the given poses), squared Sampson error, as stated in
+                                 ``include/onepose_two_view.h``.  Parity with COLMAP is not verified.
 * ``build_tracks`` / ``triangulate_tracks``
                               -- what the reference leaves to a COLMAP binary
                                  (``triangulation.py:122-148``).  **This project's own**: tracks
@@ -20,13 +27,14 @@ The reference's ``sfm_core`` (``run.py:140-193``) after feature extraction, stag
                                  ("Sparse reconstruction").  Parity with COLMAP is not verified.
 * ``reconstruct``             -- the chain; its result feeds ``object_builder.build_object``.
 
-The host stages are numpy only.  ``build_tracks`` and ``triangulate_tracks`` take ``device=``:
-with a GPU device the HIP kernels of ``csrc/sfm.hip`` run; with ``device=None`` the same contract
-runs on the host.
+The host stages are numpy only.  ``verify_matches``, ``build_tracks`` and ``triangulate_tracks``
+take ``device=``: with a GPU device the HIP kernels of ``csrc/two_view.hip`` and ``csrc/sfm.hip``
+run; with ``device=None`` the same contract runs on the host.
 
-Out of scope: COLMAP's geometric verification, its RANSAC triangulation and bundle adjustment,
-point colours, the sqlite database, ``model_analyzer`` statistics, PLY export, batching pairs into
-one matcher call.
+Out of scope: COLMAP's own verifier (E and H models, LO-RANSAC, cheirality tests, two-view
+geometries written to a database), its RANSAC triangulation and bundle adjustment, point colours,
+the sqlite database, ``model_analyzer`` statistics, PLY export, batching pairs into one matcher
+call.
 """
 from __future__ import annotations
 
@@ -181,6 +189,319 @@ def import_matches(pairs, matches, image_ids, min_match_score=None, *, offsets):
     if not edges:
         return np.zeros((0, 2), dtype=np.int32)
     return np.concatenate(edges).astype(np.int32)
+
+
+# ------------------------------------------------------------------ two-view verification
+TWO_VIEW_STATUS = {0: "verified", 1: "fewer matches than min_num_inliers", 2: "no model",
+                   3: "too few inliers"}
+_SQRT2 = 1.4142135623730951
+
+
+def fundamental_from_poses(T0, K0, T1, K1):
+    """``F = K1^-T [t]x R K0^-1`` with ``x1^T F x0 = 0`` for world-to-camera ``T0``, ``T1``
+    (``[4, 4]`` or ``[3, 4]``) and intrinsics ``K0``, ``K1``; host, float64, ``[3, 3]``."""
+    T0, T1 = np.asarray(T0, np.float64), np.asarray(T1, np.float64)
+    R = T1[:3, :3] @ T0[:3, :3].T
+    t = T1[:3, 3] - R @ T0[:3, 3]
+    tx = np.array([[0.0, -t[2], t[1]], [t[2], 0.0, -t[0]], [-t[1], t[0], 0.0]])
+    return (np.linalg.inv(np.asarray(K1, np.float64)).T @ tx @ R
+            @ np.linalg.inv(np.asarray(K0, np.float64)))
+
+
+def two_view_verify_device(pts0, pts1, counts, F_in=None, max_error=4.0, confidence=0.999,
+                           max_trials=10000, min_num_inliers=15, min_inlier_ratio=0.25,
+                           refine_iters=2):
+    """onepose_two_view_verify on device tensors (``pts0``, ``pts1`` float32 ``[B, P, 2]``,
+    ``counts`` int32 ``[B]``, ``F_in`` float64 ``[B, 9]`` or None) -> ``(F [B, 9], inlier_mask
+    uint8 [B, P], n_inliers, iters, status)`` tensors; nothing is synchronised."""
+    dev = pts0.device
+    B, P = pts0.shape[0], pts0.shape[1]
+    F = torch.empty(B, 9, dtype=torch.float64, device=dev)
+    mask = torch.empty(B, P, dtype=torch.uint8, device=dev)
+    n_inliers, iters, status = (torch.empty(B, dtype=torch.int32, device=dev) for _ in range(3))
+    nbytes = _lib.call("onepose_two_view_workspace_bytes", batch=B, max_points=P)
+    ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
+    _lib.run("onepose_two_view_verify", pts0=pts0, pts1=pts1, counts=counts, max_points=P, batch=B,
+             F_in=F_in, max_error=float(max_error), confidence=float(confidence),
+             max_trials=int(max_trials), min_num_inliers=int(min_num_inliers),
+             min_inlier_ratio=float(min_inlier_ratio), refine_iters=int(refine_iters), F=F,
+             inlier_mask=mask, n_inliers=n_inliers, iters=iters, status=status, workspace=ws,
+             workspace_bytes=nbytes, stream=_lib.stream_ptr(dev))
+    return F, mask, n_inliers, iters, status
+
+
+def _tv_jacobi(A):
+    """The header's J(k) on a batch [g, k, k] of symmetric matrices; every matrix takes its own
+    branches.  -> the eigenvector of the smallest eigenvalue, [g, k]."""
+    A = A.copy()
+    g, k = A.shape[0], A.shape[1]
+    V = np.tile(np.eye(k), (g, 1, 1))
+    running = np.ones(g, dtype=bool)
+    for _ in range(24):
+        rotated = np.zeros(g, dtype=bool)
+        for p in range(k - 1):
+            for q in range(p + 1, k):
+                apq, app, aqq = A[:, p, q].copy(), A[:, p, p].copy(), A[:, q, q].copy()
+                skip = (np.abs(apq) <= 1e-20 * np.sqrt(np.abs(app * aqq))) | (apq == 0.0)
+                rot = running & ~skip
+                rotated |= rot
+                theta = (aqq - app) / (2.0 * apq)
+                tt = np.where(theta >= 0.0, 1.0, -1.0) / (np.abs(theta) + np.sqrt(theta * theta + 1.0))
+                cs = 1.0 / np.sqrt(tt * tt + 1.0)
+                sn = tt * cs
+                for r in range(k):
+                    if r == p or r == q:
+                        continue
+                    arp, arq = A[:, r, p].copy(), A[:, r, q].copy()
+                    A[:, r, p] = A[:, p, r] = np.where(rot, cs * arp - sn * arq, arp)
+                    A[:, r, q] = A[:, q, r] = np.where(rot, sn * arp + cs * arq, arq)
+                bpp, bpq = cs * app - sn * apq, sn * app + cs * apq
+                bqp, bqq = cs * apq - sn * aqq, sn * apq + cs * aqq
+                A[:, p, p] = np.where(rot, cs * bpp - sn * bqp, app)
+                A[:, q, q] = np.where(rot, sn * bpq + cs * bqq, aqq)
+                A[:, p, q] = A[:, q, p] = np.where(running, 0.0, apq)
+                vp, vq = V[:, :, p].copy(), V[:, :, q].copy()
+                r2 = rot[:, None]
+                V[:, :, p] = np.where(r2, cs[:, None] * vp - sn[:, None] * vq, vp)
+                V[:, :, q] = np.where(r2, sn[:, None] * vp + cs[:, None] * vq, vq)
+        running &= rotated
+        if not running.any():
+            break
+    best = np.zeros(g, dtype=np.int64)
+    rows = np.arange(g)
+    for j in range(1, k):
+        best = np.where(A[rows, j, j] < A[rows, best, best], j, best)
+    return V[rows, :, best]
+
+
+def _tv_solve(X, S):
+    """The header's solver S(list) on a batch: X [g, L, 4] = (x0, y0, x1, y1) float64, S [g, L]
+    which positions belong to the list (in ascending position) -> F [g, 9]."""
+    g, L = S.shape
+    m = S.sum(1).astype(np.float64)
+    c = np.zeros((g, 4))
+    for p in range(L):
+        c = np.where(S[:, p, None], c + X[:, p], c)
+    c = c / m[:, None]
+    d = np.zeros((g, 2))
+    for p in range(L):
+        dx = X[:, p] - c
+        r = np.sqrt(np.stack([dx[:, 0] * dx[:, 0] + dx[:, 1] * dx[:, 1],
+                              dx[:, 2] * dx[:, 2] + dx[:, 3] * dx[:, 3]], 1))
+        d = np.where(S[:, p, None], d + r, d)
+    s = _SQRT2 / (d / m[:, None])
+    iu, ju = np.triu_indices(9)
+    M = np.zeros((g, 45))
+    one = np.ones(g)
+    for p in range(L):
+        u0, v0 = (X[:, p, 0] - c[:, 0]) * s[:, 0], (X[:, p, 1] - c[:, 1]) * s[:, 0]
+        u1, v1 = (X[:, p, 2] - c[:, 2]) * s[:, 1], (X[:, p, 3] - c[:, 3]) * s[:, 1]
+        a = np.stack([u1 * u0, u1 * v0, u1, v1 * u0, v1 * v0, v1, u0, v0, one], 1)
+        M = np.where(S[:, p, None], M + a[:, iu] * a[:, ju], M)
+    A = np.zeros((g, 9, 9))
+    A[:, iu, ju] = M
+    A[:, ju, iu] = M
+    N = _tv_jacobi(A).reshape(g, 3, 3)
+    G = np.empty((g, 3, 3))
+    for i in range(3):
+        for j in range(3):
+            G[:, i, j] = (N[:, 0, i] * N[:, 0, j] + N[:, 1, i] * N[:, 1, j]) + N[:, 2, i] * N[:, 2, j]
+    v = _tv_jacobi(G)
+    w = (N[:, :, 0] * v[:, None, 0] + N[:, :, 1] * v[:, None, 1]) + N[:, :, 2] * v[:, None, 2]
+    N = N - w[:, :, None] * v[:, None, :]
+    a0, a1 = N[:, :, 0] * s[:, None, 0], N[:, :, 1] * s[:, None, 0]
+    a2 = (N[:, :, 2] - a0 * c[:, None, 0]) - a1 * c[:, None, 1]
+    Am = np.stack([a0, a1, a2], 2)   # [g, i, j]
+    f0, f1 = s[:, None, 1] * Am[:, 0, :], s[:, None, 1] * Am[:, 1, :]
+    f2 = (Am[:, 2, :] - c[:, None, 2] * f0) - c[:, None, 3] * f1
+    return np.concatenate([f0, f1, f2], 1)
+
+
+def _tv_inliers(F, X, n, thr2):
+    """[.., 9] models against X [L, 4] (the first n positions count) -> bool [.., L]."""
+    F = F[..., None, :]
+    x0, y0, x1, y1 = X[:, 0], X[:, 1], X[:, 2], X[:, 3]
+    a0 = (F[..., 0] * x0 + F[..., 1] * y0) + F[..., 2]
+    a1 = (F[..., 3] * x0 + F[..., 4] * y0) + F[..., 5]
+    a2 = (F[..., 6] * x0 + F[..., 7] * y0) + F[..., 8]
+    b0 = (F[..., 0] * x1 + F[..., 3] * y1) + F[..., 6]
+    b1 = (F[..., 1] * x1 + F[..., 4] * y1) + F[..., 7]
+    e = (x1 * a0 + y1 * a1) + a2
+    err = (e * e) / (((a0 * a0 + a1 * a1) + b0 * b0) + b1 * b1)
+    ok = np.isfinite(F).all(-1)
+    return (err <= thr2) & ok & (np.arange(len(X)) < n)
+
+
+def _tv_num_iters(p, ep, max_iters):
+    """RANSACUpdateNumIters with 8 model points."""
+    tiny = 2.2250738585072014e-308
+    num = max(1.0 - min(max(p, 0.0), 1.0), tiny)
+    denom = 1.0 - (1.0 - min(max(ep, 0.0), 1.0)) ** 8
+    if denom < tiny:
+        return 0
+    num, denom = np.log(num), np.log(denom)
+    return max_iters if denom >= 0 or -num >= max_iters * (-denom) else int(np.rint(num / denom))
+
+
+def _host_two_view(pts0, pts1, counts, F_in, max_error, confidence, max_trials, min_num_inliers,
+                   min_inlier_ratio, refine_iters, chunk=64):
+    """onepose_two_view_verify's contract on the host: the hypotheses of a round of 64 iterations
+    of up to `chunk` pairs are solved in one batch, every step in the header's order, and each
+    pair replays the acceptance rule in iteration order."""
+    B, P = pts0.shape[0], pts0.shape[1]
+    X = np.concatenate([pts0, pts1], 2).astype(np.float64)   # [B, P, 4]
+    n = np.clip(np.asarray(counts, np.int64), 0, P)
+    thr2 = float(max_error) * float(max_error)
+    F = np.zeros((B, 9)) if F_in is None else np.array(F_in, np.float64).reshape(B, 9)
+    mask = np.zeros((B, P), bool)
+    iters = np.zeros(B, np.int32)
+    status = np.where(n < min_num_inliers, 1, 0).astype(np.int32)
+    run = np.nonzero(status == 0)[0]
+    with np.errstate(all="ignore"):
+        if F_in is not None:
+            for b in run:
+                mask[b] = _tv_inliers(F[b], X[b], n[b], thr2)
+        else:
+            state = {b: [0xFFFFFFFFFFFFFFFF, 0, max(int(max_trials), 1), 0] for b in run}
+            active = list(run)
+            while active:
+                for c0 in range(0, len(active), chunk):
+                    part = active[c0:c0 + chunk]
+                    sub = np.empty((len(part), 64, 8), np.int64)
+                    for a, b in enumerate(part):   # 64 subsets of 8 distinct indices per pair
+                        z, nb = state[b][0], int(n[b])
+                        for h in range(64):
+                            got = []
+                            while len(got) < 8:
+                                z = ((z & 0xFFFFFFFF) * 4164903690 + (z >> 32)) & 0xFFFFFFFFFFFFFFFF
+                                v = (z & 0xFFFFFFFF) % nb
+                                if v not in got:
+                                    got.append(v)
+                            sub[a, h] = got
+                        state[b][0] = z
+                    pb = np.asarray(part)[:, None, None]
+                    hyp = _tv_solve(X[pb, sub].reshape(-1, 8, 4),
+                                    np.ones((len(part) * 64, 8), bool)).reshape(len(part), 64, 9)
+                    for a, b in enumerate(part):
+                        good = _tv_inliers(hyp[a], X[b], n[b], thr2).sum(1)
+                        _, it, niters, best = state[b]
+                        for h in range(64):
+                            if it >= niters:
+                                break
+                            if good[h] > max(best, 7):
+                                best = int(good[h])
+                                F[b] = hyp[a, h]
+                                niters = _tv_num_iters(confidence, (int(n[b]) - best) / int(n[b]),
+                                                       niters)
+                            it += 1
+                        state[b][1:] = [it, niters, best]
+                active = [b for b in active if state[b][1] < state[b][2]]
+            for b in run:
+                iters[b] = state[b][1]
+                if state[b][3] <= 0:
+                    status[b] = 2
+                    F[b] = 0.0
+            run = np.nonzero(status == 0)[0]
+            for b in run:
+                mask[b] = _tv_inliers(F[b], X[b], n[b], thr2)
+            going = list(run)
+            for _ in range(int(refine_iters)):
+                if not going:
+                    break
+                L = int(n[going].max())
+                cand = _tv_solve(X[going][:, :L], mask[going][:, :L])
+                kept = []
+                for a, b in enumerate(going):
+                    cm = _tv_inliers(cand[a], X[b], n[b], thr2)
+                    if np.isfinite(cand[a]).all() and cm.sum() >= mask[b].sum():
+                        F[b], mask[b] = cand[a], cm
+                        kept.append(b)
+                going = kept
+    nin = mask.sum(1).astype(np.int32)
+    weak = (nin < min_num_inliers) | (nin.astype(np.float64) < min_inlier_ratio * n.astype(np.float64))
+    status[(status == 0) & weak] = 3
+    return F, mask.astype(np.uint8), nin, iters, status
+
+
+def verify_matches(pairs, matches, features, geometry="estimate", poses=None, Ks=None,
+                   img_lists=None, max_error=4.0, confidence=0.999, max_trials=10000,
+                   min_num_inliers=15, min_inlier_ratio=0.25, refine_iters=2, device=None):
+    """Two-view geometric verification of ``match_pairs``' output, every pair in one padded call.
+    ``geometry="estimate"``: a fundamental matrix per pair by RANSAC; ``"poses"``: the F of the
+    given world-to-camera ``poses [m, 4, 4]`` and ``Ks [m, 3, 3]`` (in the order of
+    ``img_lists``).  Matches are scored at keypoint + 0.5 in float32.
+
+    Returns ``(verified, report)``.  ``verified`` is a new mapping like ``matches``: a rejected
+    match has ``matches0[i] = -1``, every match of a pair whose status is not 0 has, and
+    ``matches1[j] = -1`` where ``j``'s partner was rejected; scores are copied unchanged.
+    ``report[pair]`` holds ``status`` (``TWO_VIEW_STATUS``), ``n_matches``, ``n_inliers``,
+    ``iters`` and ``F [3, 3]``.  The library's contract is in ``include/onepose_two_view.h``; with
+    ``device=None`` the same contract runs on the host."""
+    if geometry not in ("estimate", "poses"):
+        raise ValueError(f"verify_matches: geometry {geometry!r} is not 'estimate' or 'poses'")
+    if geometry == "poses":
+        if poses is None or Ks is None or img_lists is None:
+            raise ValueError("verify_matches: geometry='poses' needs poses, Ks and img_lists")
+        index = {name: k for k, name in enumerate(img_lists)}
+        T, Kall = _load_poses(poses), np.asarray(Ks, np.float64)
+    todo, seen = [], set()
+    for name0, name1 in pairs:
+        pair = names_to_pair(name0, name1)
+        if pair in matches and pair not in seen:
+            seen.add(pair)
+            todo.append((pair, name0, name1))
+    verified = {pair: {k: np.array(v) for k, v in grp.items()} for pair, grp in matches.items()}
+    report = {}
+    if not todo:
+        return verified, report
+    sel = []
+    for pair, name0, name1 in todo:
+        m0 = np.asarray(matches[pair]["matches0"]).astype(np.int64)
+        i0 = np.nonzero(m0 > -1)[0]
+        sel.append((i0, m0[i0]))
+    P = max(1, max(len(i0) for i0, _ in sel))
+    B = len(todo)
+    pts0, pts1 = np.zeros((B, P, 2), np.float32), np.zeros((B, P, 2), np.float32)
+    counts = np.asarray([len(i0) for i0, _ in sel], np.int32)
+    F_in = np.zeros((B, 9)) if geometry == "poses" else None
+    for b, ((pair, name0, name1), (i0, i1)) in enumerate(zip(todo, sel)):
+        k0 = np.asarray(features[name0]["keypoints"], np.float32).reshape(-1, 2)
+        k1 = np.asarray(features[name1]["keypoints"], np.float32).reshape(-1, 2)
+        pts0[b, :len(i0)] = k0[i0] + np.float32(0.5)
+        pts1[b, :len(i1)] = k1[i1] + np.float32(0.5)
+        if F_in is not None:
+            a, c = index[name0], index[name1]
+            F_in[b] = fundamental_from_poses(T[a], Kall[a], T[c], Kall[c]).reshape(9)
+    opts = dict(max_error=max_error, confidence=confidence, max_trials=max_trials,
+                min_num_inliers=min_num_inliers, min_inlier_ratio=min_inlier_ratio,
+                refine_iters=refine_iters)
+    dev = _gpu(device)
+    if dev is None:
+        if min_num_inliers < 8 or max_trials < 1 or refine_iters < 0:
+            raise _lib.OnePoseError("two_view: min_num_inliers below 8, max_trials below 1 or "
+                                    "refine_iters negative")
+        F, mask, nin, iters, status = _host_two_view(pts0, pts1, counts, F_in, **opts)
+    else:
+        out = two_view_verify_device(
+            torch.from_numpy(pts0).to(dev), torch.from_numpy(pts1).to(dev),
+            torch.from_numpy(counts).to(dev),
+            None if F_in is None else torch.from_numpy(F_in).to(dev), **opts)
+        F, mask, nin, iters, status = (t.cpu().numpy() for t in out)
+    for b, ((pair, _, _), (i0, i1)) in enumerate(zip(todo, sel)):
+        keep = mask[b, :len(i0)].astype(bool) & (status[b] == 0)
+        grp = verified[pair]
+        rejected = np.zeros(len(grp["matches0"]), bool)
+        rejected[i0[~keep]] = True
+        grp["matches0"][rejected] = -1
+        if "matches1" in grp:
+            m1 = grp["matches1"].astype(np.int64)
+            back = (m1 > -1) & (m1 < len(rejected))
+            back[back] = rejected[m1[back]]
+            grp["matches1"][back] = -1
+        report[pair] = {"status": int(status[b]), "n_matches": int(counts[b]),
+                        "n_inliers": int(nin[b]), "iters": int(iters[b]),
+                        "F": np.array(F[b], np.float64).reshape(3, 3)}
+    return verified, report
 
 
 # ------------------------------------------------------------------ the model and its files
@@ -574,12 +895,15 @@ def triangulate_tracks(Rt, K4, track_start, obs_image, obs_xy, max_reproj=MAX_RE
 # ------------------------------------------------------------------ the chain
 def reconstruct(features, img_lists, poses, Ks, matcher, covis_num=10, min_match_score=None,
                 out_dir=None, device=None, seq_ids=None, max_reproj=MAX_REPROJ,
-                min_angle_deg=MIN_ANGLE_DEG, match_device=None):
+                min_angle_deg=MIN_ANGLE_DEG, match_device=None, verify=None, verify_options=None):
     """Pairs, match export, match import, tracks, triangulation and the compaction of the kept
     tracks.  ``poses``: world-to-camera ``[m, 4, 4]`` (or pose files), ``Ks [m, 3, 3]``, both in
     the order of ``img_lists``; ``features[name]`` holds ``keypoints [n, 2]``, ``image_size``
     (w, h) and whatever the matcher reads.  Point ids are 1, 2, ... in track order.  The matcher
-    gets its tensors on ``match_device`` (default: ``device``).
+    gets its tensors on ``match_device`` (default: ``device``).  ``verify``: None (no geometric
+    verification), ``"estimate"`` or ``"poses"`` -- ``verify_matches`` with that geometry (and
+    ``verify_options`` as its keywords) between the match export and the import; its report is
+    the model's ``'two_view'``.
 
     Returns one mapping with the keys of ``object_builder.read_points3d_binary`` and
     ``read_images_binary`` (and of ``empty_model``), plus ``'pairs'`` and ``'tracks'``; with
@@ -589,6 +913,11 @@ def reconstruct(features, img_lists, poses, Ks, matcher, covis_num=10, min_match
     pairs = covis_from_pose(img_lists, poses, covis_num, seq_ids=seq_ids)
     matches = match_pairs(features, pairs, matcher,
                           device=device if match_device is None else match_device)
+    two_view = None
+    if verify is not None:
+        matches, two_view = verify_matches(pairs, matches, features, geometry=verify, poses=P,
+                                           Ks=Ks, img_lists=img_lists, device=device,
+                                           **(verify_options or {}))
     sizes = [np.asarray(features[n]["image_size"]).reshape(2) for n in img_lists]
     model = empty_model(img_lists, P, Ks, sizes)
     names = model["names"]
@@ -626,6 +955,8 @@ def reconstruct(features, img_lists, poses, Ks, matcher, covis_num=10, min_match
         "track_point2D_idxs": [of[ts[t]:ts[t + 1]][keep[ts[t]:ts[t + 1]]] for t in kept],
         "pairs": pairs, "tracks": tracks, "triangulation": tri,
     })
+    if two_view is not None:
+        model["two_view"] = two_view
     if out_dir is not None:
         write_model_binary(model, out_dir)
     return model
