@@ -23,6 +23,9 @@ HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "onepose_hip.h")
 # Families added after ABI 9 declare themselves in headers of their own, which onepose_hip.h
 # includes: SIGNATURES / PROTOTYPES stay the ABI-9 header's table, FAMILY_SIGNATURES holds theirs.
 FAMILY_HEADERS = ("onepose_two_view.h",)
+# Later families: one table per header in FAMILIES ({header: signatures}), so that the tables
+# above stay what they were when their tests pinned them.
+LATER_HEADERS = ("onepose_superglue_counts.h",)
 
 c_int, c_int64, c_size_t, c_float, c_double = (ctypes.c_int, ctypes.c_int64, ctypes.c_size_t,
                                                ctypes.c_float, ctypes.c_double)
@@ -132,11 +135,23 @@ for _h in FAMILY_HEADERS:
     FAMILY_SIGNATURES.update(_sigs)
 FAMILY_PROTOTYPES = {name: (res, [t for _, t in params])
                      for name, (res, params) in FAMILY_SIGNATURES.items()}
+# header -> that header's declarations (same shape as SIGNATURES), and all of them in one table
+FAMILIES = {}
+LATER_SIGNATURES = {}
+for _h in LATER_HEADERS:
+    _sigs, _ = parse_header(_read_header(os.path.join(os.path.dirname(HEADER_PATH), _h)))
+    if set(_sigs) & (set(SIGNATURES) | set(FAMILY_SIGNATURES) | set(LATER_SIGNATURES)):
+        raise OnePoseError(f"{_h}: declares a function that another header declares")
+    FAMILIES[_h] = _sigs
+    LATER_SIGNATURES.update(_sigs)
+LATER_PROTOTYPES = {name: (res, [t for _, t in params])
+                    for name, (res, params) in LATER_SIGNATURES.items()}
 # name -> (keyword names in order, indices of the pointer parameters); a parameter named like
 # a Python keyword takes a trailing underscore (onepose_affine_partial_ransac's from_)
 _ORDER = {name: (tuple(n + "_" * keyword.iskeyword(n) for n, _ in params),
                  tuple(i for i, (_, t) in enumerate(params) if t is c_void_p))
-          for name, (_, params) in {**SIGNATURES, **FAMILY_SIGNATURES}.items()}
+          for name, (_, params) in {**SIGNATURES, **FAMILY_SIGNATURES,
+                                    **LATER_SIGNATURES}.items()}
 
 _lib = None
 
@@ -153,7 +168,7 @@ def load():
         # A/B measurement only: an older build named by ONEPOSE_LIB may predate the newest
         # entry points (ABI >= 3); callers fall back where one is missing (size_query)
         ab = bool(os.environ.get("ONEPOSE_LIB"))
-        for name, (res, args) in {**PROTOTYPES, **FAMILY_PROTOTYPES}.items():
+        for name, (res, args) in {**PROTOTYPES, **FAMILY_PROTOTYPES, **LATER_PROTOTYPES}.items():
             if ab and not hasattr(lib, name):
                 continue
             fn = getattr(lib, name)

@@ -108,6 +108,8 @@ struct SgSideIn {
   int64_t desc_bs, kpts_bs, scores_bs;   // elements; 0 = shared by the batch
   int n;
   float cx, cy, scale;   // normalize_keypoints: centre (w/2, h/2), 0.7 * max(w, h)
+  const int* counts;     // counts entries: [B] real tokens per sample, or null (all n)
+  const int* hw;         // counts entries: [B][2] (h, w) per sample, or null (cx, cy, scale above)
   float* xd;   // [B][n][256] descriptors, token-major
   float* h3;   // [B][n][128] encoder layer 3 output after ReLU
   int tiles;   // workgroups per sample of the kernel at hand
@@ -117,7 +119,20 @@ struct SgInArgs {
   int batch;
 };
 
+// A sample's own token count in the entries that take counts: read on the device, clamped to
+// [0, n]; a null array is "every sample has n".  Every kernel below has a CNT = false
+// instantiation, which the uniform entries launch and which never looks at the arrays, and a
+// CNT = true one for the counts entries, where n (m) of sample b comes from here while the
+// strides and the grid stay those of the batch maxima.
+__device__ __forceinline__ int sg_count(const int* counts, int b, int n) {
+  if (counts == nullptr) return n;
+  const int c = counts[b];
+  return c < 0 ? 0 : (c > n ? n : c);
+}
+
 // [B][256][n] -> [B][n][256], 64 tokens x 64 channels per workgroup through a padded LDS tile.
+// CNT: tokens past the sample's count are written as zero rows.
+template <bool CNT>
 __global__ __launch_bounds__(256) void sg_transpose_kernel(SgInArgs args) {
   __shared__ float tile[64][65];
   int bid = blockIdx.x;
@@ -126,11 +141,12 @@ __global__ __launch_bounds__(256) void sg_transpose_kernel(SgInArgs args) {
   if (second) bid -= args.p[0].tiles * args.batch;
   const int b = bid / P.tiles, r = bid - b * P.tiles;
   const int n0 = (r >> 2) * 64, c0 = (r & 3) * 64, n = P.n;
+  const int nb = CNT ? sg_count(P.counts, b, n) : n;
   const float* s = P.desc + (int64_t)b * P.desc_bs;
   const int t = threadIdx.x;
   for (int i = 0; i < 16; ++i) {
     const int ch = (t >> 6) + 4 * i, tk = t & 63;
-    tile[ch][tk] = (n0 + tk < n) ? s[(int64_t)(c0 + ch) * n + n0 + tk] : 0.f;
+    tile[ch][tk] = (n0 + tk < nb) ? s[(int64_t)(c0 + ch) * n + n0 + tk] : 0.f;
   }
   __syncthreads();
   float* d = P.xd + (int64_t)b * n * kDim;
@@ -146,7 +162,10 @@ __global__ __launch_bounds__(256) void sg_transpose_kernel(SgInArgs args) {
 // normalize_keypoints + the encoder's first three layers (3 -> 32 -> 64 -> 128, BatchNorm folded,
 // ReLU), eight tokens per workgroup: a thread owns one output channel of all eight, so a weight
 // is loaded once per eight FMAs.  Layers 4 and 5 (K = 128, 256) are token GEMMs.
+// CNT: centre and scale from the sample's own (h, w) (values below 1 read as 1), and zero rows past
+// the sample's count.
 constexpr int kKencTok = 8;
+template <bool CNT>
 __global__ __launch_bounds__(128) void sg_kenc_kernel(SgInArgs args, const float* __restrict__ w) {
   __shared__ float in[kKencTok][4], h1[kKencTok][32], h2[kKencTok][64];
   int bid = blockIdx.x;
@@ -154,13 +173,22 @@ __global__ __launch_bounds__(128) void sg_kenc_kernel(SgInArgs args, const float
   const SgSideIn& P = second ? args.p[1] : args.p[0];
   if (second) bid -= args.p[0].tiles * args.batch;
   const int b = bid / P.tiles, t0 = (bid - b * P.tiles) * kKencTok, t = threadIdx.x;
+  const int nb = CNT ? sg_count(P.counts, b, P.n) : P.n;
   if (t < kKencTok) {
     const int tok = t0 + t;
     float x = 0.f, y = 0.f, sc = 0.f;
-    if (tok < P.n) {
+    if (tok < nb) {
+      float cx = P.cx, cy = P.cy, scale = P.scale;
+      if (CNT && P.hw != nullptr) {   // the host's arithmetic (sg_forward), per sample
+        const int hi = P.hw[2 * b], wi = P.hw[2 * b + 1];
+        const float h = (float)(hi < 1 ? 1 : hi), w = (float)(wi < 1 ? 1 : wi);
+        cx = w / 2.f;
+        cy = h / 2.f;
+        scale = (w > h ? w : h) * 0.7f;
+      }
       const float* kp = P.kpts + (int64_t)b * P.kpts_bs + (int64_t)tok * 2;
-      x = (kp[0] - P.cx) / P.scale;
-      y = (kp[1] - P.cy) / P.scale;
+      x = (kp[0] - cx) / scale;
+      y = (kp[1] - cy) / scale;
       sc = P.scores[(int64_t)b * P.scores_bs + tok];
     }
     in[t][0] = x;
@@ -202,7 +230,7 @@ __global__ __launch_bounds__(128) void sg_kenc_kernel(SgInArgs args, const float
     float* o = P.h3 + ((int64_t)b * P.n + t0) * 128 + t;
 #pragma unroll
     for (int k = 0; k < kKencTok; ++k)
-      if (t0 + k < P.n) o[(int64_t)k * 128] = fmaxf(acc[k], 0.f);
+      if (t0 + k < P.n) o[(int64_t)k * 128] = (!CNT || t0 + k < nb) ? fmaxf(acc[k], 0.f) : 0.f;
   }
 }
 
@@ -228,6 +256,7 @@ struct AttnProb {
   int ldq, ldk, ldv, ldo;           // row strides, elements (multiples of 4)
   int n, m;                         // queries, keys
   int qtiles;                       // ceil(n / (32 NW))
+  const int *counts_q, *counts_k;   // counts entries: [B] real queries / keys, or null (n / m)
 };
 struct AttnArgs {
   AttnProb p[2];
@@ -240,9 +269,16 @@ __device__ __forceinline__ int ceil_div_dev(int a, int b) { return (a + b - 1) /
 // (NW = 1; small problems, where 32-query tiles alone leave most SIMDs idle): the four waves own
 // the SAME 32 queries and every fourth key tile each, staged in a private LDS region per wave;
 // their (max, sum, O) states are merged through LDS in wave order at the end, a fixed order.
+//
+// CNT: n and m are sample b's own counts.  b is fixed per workgroup, so the trip count (from m)
+// and with it every barrier stays uniform within the workgroup; a wave whose queries all lie past
+// the sample's n stages tiles and meets the barriers like the others.  Query rows from the
+// sample's n up to the batch's n are written as zeros, and so is every row of a sample without
+// keys (its sum is 0; nothing is divided by it).  With KS = 4 a short sample leaves waves without
+// a key tile: their max stays -inf and the merge skips them, per sample as before per launch.
 constexpr int kAttnTileFloats = kAttnKT * kAttnKP + kAttnKT * 64;
 
-template <int NW, int KS>
+template <int NW, int KS, bool CNT>
 __global__ __launch_bounds__(NW * KS * 64) void mha_softmax_kernel(AttnArgs args) {
   typedef float floatx16 __attribute__((ext_vector_type(16)));
   extern __shared__ __attribute__((aligned(16))) float attn_lds[];
@@ -257,7 +293,8 @@ __global__ __launch_bounds__(NW * KS * 64) void mha_softmax_kernel(AttnArgs args
   const int wq = KS > 1 ? 0 : w, ks = KS > 1 ? w : 0;
   float* Ks = attn_lds + (KS > 1 ? w * kAttnTileFloats : 0);
   float* Vs = Ks + kAttnKT * kAttnKP;
-  const int n = P.n, m = P.m;
+  const int n = CNT ? sg_count(P.counts_q, b, P.n) : P.n;
+  const int m = CNT ? sg_count(P.counts_k, b, P.m) : P.m;
   const int q0 = (qt * NW + wq) * 32, query = q0 + l31;
   const bool active = q0 < n;   // wave-uniform
 
@@ -371,9 +408,22 @@ __global__ __launch_bounds__(NW * KS * 64) void mha_softmax_kernel(AttnArgs args
       mrun = M;
     }
   }
-  if (!active) return;
-  if (query >= n) return;
   float* op = P.o + (int64_t)b * P.o_bs + (int64_t)query * P.ldo + h * 64 + 4 * hh;
+  if (CNT) {
+    if (query >= P.n) return;
+    if (query >= n || m == 0) {   // a padded query row, or a sample without keys
+      const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll
+      for (int g = 0; g < 4; ++g) {
+        *reinterpret_cast<float4*>(op + 8 * g) = z;
+        *reinterpret_cast<float4*>(op + 32 + 8 * g) = z;
+      }
+      return;
+    }
+  } else {
+    if (!active) return;
+    if (query >= n) return;
+  }
 #pragma unroll
   for (int g = 0; g < 4; ++g) {
     *reinterpret_cast<float4*>(op + 8 * g) = make_float4(
@@ -383,6 +433,7 @@ __global__ __launch_bounds__(NW * KS * 64) void mha_softmax_kernel(AttnArgs args
   }
 }
 
+template <bool CNT>
 int attn_launch(AttnArgs& a, int nprob, hipStream_t st) {
   constexpr size_t kTileBytes = (size_t)kAttnTileFloats * 4;
   // small problems (32-query tiles give at most two waves per CU, and there are key tiles to
@@ -408,22 +459,22 @@ int attn_launch(AttnArgs& a, int nprob, hipStream_t st) {
   }
   OP_REQUIRE(grid > 0 && grid < (1ll << 31), "mha_softmax: grid of %lld workgroups", (long long)grid);
   if (split) {
-    static bool attr_set = false;
+    static bool attr_set = false;   // (one per instantiation of this function)
     if (!attr_set) {
-      OP_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(mha_softmax_kernel<1, 4>),
+      OP_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(mha_softmax_kernel<1, 4, CNT>),
                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)(4 * kTileBytes)));
       attr_set = true;
     }
-    OP_LAUNCH(K_SG_ATTN, st, (mha_softmax_kernel<1, 4>), dim3((unsigned)grid), dim3(256),
+    OP_LAUNCH(K_SG_ATTN, st, (mha_softmax_kernel<1, 4, CNT>), dim3((unsigned)grid), dim3(256),
               4 * kTileBytes, st, a);
   } else if (nw == 4) {
-    OP_LAUNCH(K_SG_ATTN, st, (mha_softmax_kernel<4, 1>), dim3((unsigned)grid), dim3(256), kTileBytes,
+    OP_LAUNCH(K_SG_ATTN, st, (mha_softmax_kernel<4, 1, CNT>), dim3((unsigned)grid), dim3(256), kTileBytes,
               st, a);
   } else if (nw == 2) {
-    OP_LAUNCH(K_SG_ATTN, st, (mha_softmax_kernel<2, 1>), dim3((unsigned)grid), dim3(128), kTileBytes,
+    OP_LAUNCH(K_SG_ATTN, st, (mha_softmax_kernel<2, 1, CNT>), dim3((unsigned)grid), dim3(128), kTileBytes,
               st, a);
   } else {
-    OP_LAUNCH(K_SG_ATTN, st, (mha_softmax_kernel<1, 1>), dim3((unsigned)grid), dim3(64), kTileBytes,
+    OP_LAUNCH(K_SG_ATTN, st, (mha_softmax_kernel<1, 1, CNT>), dim3((unsigned)grid), dim3(64), kTileBytes,
               st, a);
   }
   return ONEPOSE_OK;
@@ -459,7 +510,40 @@ struct SkArgs {
   double2* part;          // [B][chunks][n+1] column-pass partials
   int chunks, rows;       // column-pass chunks and rows per chunk (one chunk: all rows)
   double norm, log_mu_bin, log_nu_bin;
+  const int *counts_m, *counts_n;   // counts entries: [B] real rows / columns, or null (m / n)
 };
+
+// One sample's problem inside the padded layout (the CNT = true kernels): its own m x n, and
+// norm / log_mu_bin / log_nu_bin of those in float64 on the device.  The strides (u, v, the
+// partials, the outputs) and the chunking stay those of A.m and A.n, the batch maxima.  A sample
+// with m = 0 or n = 0 has no transport problem: every kernel leaves it at once (b is fixed per
+// workgroup, so no barrier is split) and sg_mutual_kernel writes its "no match" rows.
+struct SkDims {
+  int m, n;
+  bool empty;
+};
+template <bool CNT>
+__device__ __forceinline__ SkDims sk_dims(const SkArgs& A, int b) {
+  SkDims d{A.m, A.n, false};
+  if (CNT) {
+    d.m = sg_count(A.counts_m, b, A.m);
+    d.n = sg_count(A.counts_n, b, A.n);
+    d.empty = d.m == 0 || d.n == 0;
+  }
+  return d;
+}
+template <bool CNT>
+__device__ __forceinline__ double sk_norm(const SkArgs& A, const SkDims& d) {
+  return CNT ? -log((double)d.m + (double)d.n) : A.norm;
+}
+template <bool CNT>
+__device__ __forceinline__ double sk_log_mu_bin(const SkArgs& A, const SkDims& d) {
+  return CNT ? log((double)d.n) + sk_norm<true>(A, d) : A.log_mu_bin;
+}
+template <bool CNT>
+__device__ __forceinline__ double sk_log_nu_bin(const SkArgs& A, const SkDims& d) {
+  return CNT ? log((double)d.m) + sk_norm<true>(A, d) : A.log_nu_bin;
+}
 
 // exp of a non-positive argument for a sum: v_exp_f32 on x * log2(e).  The product's rounding
 // makes the relative error |x| * 2^-24, so the absolute error is at most max(x e^-x) * 2^-24 =
@@ -491,10 +575,12 @@ __global__ __launch_bounds__(256) void sk_init_kernel(SkArgs A) {
   if (i <= A.n) A.v[(int64_t)b * A.v_bs + i] = 0.0;
 }
 
+template <bool CNT>
 __global__ __launch_bounds__(256) void sk_row_kernel(SkArgs A) {
   const int b = blockIdx.y, lane = threadIdx.x & 63;
-  const int i = blockIdx.x * 4 + (threadIdx.x >> 6), m = A.m, n = A.n;
-  if (i > m) return;
+  const SkDims D = sk_dims<CNT>(A, b);
+  const int i = blockIdx.x * 4 + (threadIdx.x >> 6), m = D.m, n = D.n;
+  if (D.empty || i > m) return;
   const double a = sk_alpha(A);
   const double* v = A.v + (int64_t)b * A.v_bs;
   double mx = -INFINITY, s = 0.0;
@@ -523,17 +609,23 @@ __global__ __launch_bounds__(256) void sk_row_kernel(SkArgs A) {
   const double M = wave_max_d(mx);
   s = wave_sum_d(mx == -INFINITY ? 0.0 : s * exp(mx - M));
   if (lane == 0)
-    A.u[(int64_t)b * (m + 1) + i] = (i < m ? A.norm : A.log_mu_bin) - (M + log(s));
+    A.u[(int64_t)b * (A.m + 1) + i] =
+        (i < m ? sk_norm<CNT>(A, D) : sk_log_mu_bin<CNT>(A, D)) - (M + log(s));
 }
 
 // grid (ceil((n+1)/64), chunks, B): 64 columns x one row chunk; wave w takes rows r0 + w + 4 k
+// CNT: the chunks are those of the batch's m; a chunk past the sample's dustbin row (row m of the
+// sample) has no rows and leaves the empty partial (-inf, 0), which lse_merge passes over.
+template <bool CNT>
 __global__ __launch_bounds__(256) void sk_col_kernel(SkArgs A) {
   __shared__ double red_m[4][64], red_s[4][64];
   const int b = blockIdx.z, c = blockIdx.y, lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  const int j = blockIdx.x * 64 + lane, m = A.m, n = A.n;
+  const SkDims D = sk_dims<CNT>(A, b);
+  if (D.empty) return;   // the whole workgroup
+  const int j = blockIdx.x * 64 + lane, m = D.m, n = D.n;
   const int r0 = c * A.rows, r1 = min(r0 + A.rows, m + 1);
   const double a = sk_alpha(A);
-  const double* u = A.u + (int64_t)b * (m + 1);
+  const double* u = A.u + (int64_t)b * (A.m + 1);
   const float* Sc = A.S + (int64_t)b * A.s_bs + j;
   double mx = -INFINITY, s = 0.0;
   if (j <= n) {
@@ -558,21 +650,26 @@ __global__ __launch_bounds__(256) void sk_col_kernel(SkArgs A) {
 #pragma unroll
   for (int q = 1; q < 4; ++q) lse_merge(mx, s, red_m[q][lane], red_s[q][lane]);
   if (A.chunks == 1)
-    A.v[(int64_t)b * A.v_bs + j] = (j < n ? A.norm : A.log_nu_bin) - (mx + log(s));
+    A.v[(int64_t)b * A.v_bs + j] =
+        (j < n ? sk_norm<CNT>(A, D) : sk_log_nu_bin<CNT>(A, D)) - (mx + log(s));
   else
-    A.part[((int64_t)b * A.chunks + c) * (n + 1) + j] = make_double2(mx, s);
+    A.part[((int64_t)b * A.chunks + c) * (A.n + 1) + j] = make_double2(mx, s);
 }
 
+template <bool CNT>
 __global__ __launch_bounds__(256) void sk_colmerge_kernel(SkArgs A) {
-  const int b = blockIdx.y, j = blockIdx.x * 256 + threadIdx.x, n = A.n;
-  if (j > n) return;
-  const double2* p = A.part + (int64_t)b * A.chunks * (n + 1) + j;
+  const int b = blockIdx.y, j = blockIdx.x * 256 + threadIdx.x;
+  const SkDims D = sk_dims<CNT>(A, b);
+  const int n = D.n;
+  if (D.empty || j > n) return;
+  const double2* p = A.part + (int64_t)b * A.chunks * (A.n + 1) + j;
   double mx = -INFINITY, s = 0.0;
   for (int c = 0; c < A.chunks; ++c) {
-    const double2 q = p[(int64_t)c * (n + 1)];
+    const double2 q = p[(int64_t)c * (A.n + 1)];
     lse_merge(mx, s, q.x, q.y);
   }
-  A.v[(int64_t)b * A.v_bs + j] = (j < n ? A.norm : A.log_nu_bin) - (mx + log(s));
+  A.v[(int64_t)b * A.v_bs + j] =
+      (j < n ? sk_norm<CNT>(A, D) : sk_log_nu_bin<CNT>(A, D)) - (mx + log(s));
 }
 
 // Z + u + v - norm in the reference's order (float64, rounded to fp32 once), written to `out`
@@ -582,21 +679,26 @@ struct SkBest {
   float val;
   int idx;
 };
+// CNT: sample b's (m+1) x (n+1) matrix is the top-left block of its padded slot in `out` (dustbin
+// row at the sample's m, dustbin column at its n); nothing outside the block is written.
+template <bool CNT>
 __global__ __launch_bounds__(256) void sk_finish_row_kernel(SkArgs A, float* out, float* rowmax,
                                                             int* rowidx) {
   const int b = blockIdx.y, lane = threadIdx.x & 63;
-  const int i = blockIdx.x * 4 + (threadIdx.x >> 6), m = A.m, n = A.n;
-  if (i > m || (out == nullptr && i == m)) return;
-  const double a = sk_alpha(A), ui = A.u[(int64_t)b * (m + 1) + i];
+  const SkDims D = sk_dims<CNT>(A, b);
+  const int i = blockIdx.x * 4 + (threadIdx.x >> 6), m = D.m, n = D.n;
+  if (D.empty || i > m || (out == nullptr && i == m)) return;
+  const double a = sk_alpha(A), ui = A.u[(int64_t)b * (A.m + 1) + i];
+  const double norm = sk_norm<CNT>(A, D);
   const double* v = A.v + (int64_t)b * A.v_bs;
   const float* row = A.S + (int64_t)b * A.s_bs + (int64_t)i * A.ld;
-  float* o = out != nullptr ? out + ((int64_t)b * (m + 1) + i) * (n + 1) : nullptr;
+  float* o = out != nullptr ? out + ((int64_t)b * (A.m + 1) + i) * (A.n + 1) : nullptr;
   float best = -INFINITY;
   int bi = 0x7fffffff;
 #pragma unroll 4
   for (int j = lane; j <= n; j += 64) {
     const bool inner = i < m && j < n;
-    const float z = (float)((((inner ? (double)row[j] : a) + ui) + v[j]) - A.norm);
+    const float z = (float)((((inner ? (double)row[j] : a) + ui) + v[j]) - norm);
     if (o != nullptr) o[j] = z;
     if (inner && z > best) {
       best = z;
@@ -614,19 +716,23 @@ __global__ __launch_bounds__(256) void sk_finish_row_kernel(SkArgs A, float* out
     }
   }
   if (lane == 0) {
-    rowmax[(int64_t)b * m + i] = best;
-    rowidx[(int64_t)b * m + i] = bi == 0x7fffffff ? 0 : bi;
+    rowmax[(int64_t)b * A.m + i] = best;
+    rowidx[(int64_t)b * A.m + i] = bi == 0x7fffffff ? 0 : bi;
   }
 }
 
 // Column winners over Z[:m, :n] per row chunk (grid (ceil(n/64), chunks, B)), lowest row on ties.
+template <bool CNT>
 __global__ __launch_bounds__(256) void sk_finish_col_kernel(SkArgs A, SkBest* cpart) {
   __shared__ float red_v[4][64];
   __shared__ int red_i[4][64];
   const int b = blockIdx.z, c = blockIdx.y, lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  const int j = blockIdx.x * 64 + lane, m = A.m, n = A.n;
+  const SkDims D = sk_dims<CNT>(A, b);
+  if (D.empty) return;   // the whole workgroup
+  const int j = blockIdx.x * 64 + lane, m = D.m, n = D.n;
   const int r0 = c * A.rows, r1 = min(r0 + A.rows, m);
-  const double* u = A.u + (int64_t)b * (m + 1);
+  const double* u = A.u + (int64_t)b * (A.m + 1);
+  const double norm = sk_norm<CNT>(A, D);
   float best = -INFINITY;
   int bi = 0x7fffffff;
   if (j < n) {
@@ -634,7 +740,7 @@ __global__ __launch_bounds__(256) void sk_finish_col_kernel(SkArgs A, SkBest* cp
     const double vj = A.v[(int64_t)b * A.v_bs + j];
 #pragma unroll 4
     for (int i = r0 + w; i < r1; i += 4) {
-      const float z = (float)((((double)Sc[(int64_t)i * A.ld] + u[i]) + vj) - A.norm);
+      const float z = (float)((((double)Sc[(int64_t)i * A.ld] + u[i]) + vj) - norm);
       if (z > best) {
         best = z;
         bi = i;
@@ -654,29 +760,47 @@ __global__ __launch_bounds__(256) void sk_finish_col_kernel(SkArgs A, SkBest* cp
       bi = oi;
     }
   }
-  cpart[((int64_t)b * A.chunks + c) * n + j] = SkBest{best, bi};
+  cpart[((int64_t)b * A.chunks + c) * A.n + j] = SkBest{best, bi};
 }
 
-// Mutual check and threshold (superglue.py:310-320).  One workgroup per sample.
+// Mutual check and threshold (superglue.py:310-320).  One workgroup per sample.  CNT (mm, nn: the
+// batch's m and n, the strides): entries past the sample's counts, and every entry of a sample
+// with an empty side (the reference's empty branch for that pair), are -1 and 0.
+template <bool CNT>
 __global__ __launch_bounds__(1024) void sg_mutual_kernel(const float* rowmax, const int* rowidx,
-                                                         const SkBest* cpart, int chunks, int m,
-                                                         int n, float thr, int* colidx,
+                                                         const SkBest* cpart, int chunks, int mm,
+                                                         int nn, float thr, int* colidx,
                                                          int64_t* matches0, int64_t* matches1,
-                                                         float* mscores0, float* mscores1) {
+                                                         float* mscores0, float* mscores1,
+                                                         const int* counts_m, const int* counts_n) {
   const int b = blockIdx.x;
-  rowmax += (int64_t)b * m;
-  rowidx += (int64_t)b * m;
-  cpart += (int64_t)b * chunks * n;
-  colidx += (int64_t)b * n;
-  matches0 += (int64_t)b * m;
-  mscores0 += (int64_t)b * m;
-  matches1 += (int64_t)b * n;
-  mscores1 += (int64_t)b * n;
+  rowmax += (int64_t)b * mm;
+  rowidx += (int64_t)b * mm;
+  cpart += (int64_t)b * chunks * nn;
+  colidx += (int64_t)b * nn;
+  matches0 += (int64_t)b * mm;
+  mscores0 += (int64_t)b * mm;
+  matches1 += (int64_t)b * nn;
+  mscores1 += (int64_t)b * nn;
+  int m = mm, n = nn;
+  if (CNT) {
+    m = sg_count(counts_m, b, mm);
+    n = sg_count(counts_n, b, nn);
+    if (m == 0 || n == 0) m = n = 0;
+    for (int i = m + threadIdx.x; i < mm; i += 1024) {
+      matches0[i] = (int64_t)-1;
+      mscores0[i] = 0.f;
+    }
+    for (int j = n + threadIdx.x; j < nn; j += 1024) {
+      matches1[j] = (int64_t)-1;
+      mscores1[j] = 0.f;
+    }
+  }
   for (int j = threadIdx.x; j < n; j += 1024) {
     float best = -INFINITY;
     int bi = 0;
     for (int c = 0; c < chunks; ++c) {   // ascending rows: a later chunk wins only if larger
-      const SkBest q = cpart[(int64_t)c * n + j];
+      const SkBest q = cpart[(int64_t)c * nn + j];
       if (q.val > best) {
         best = q.val;
         bi = q.idx;
@@ -704,6 +828,9 @@ __global__ __launch_bounds__(1024) void sg_mutual_kernel(const float* rowmax, co
 int sk_chunks(int rows) { return rows <= 2 * kSkRows ? 1 : ceil_div(rows, kSkRows); }
 
 // u, v for `iters` iterations (A.S / ld / m / n / alpha / u / v / part set by the caller).
+// CNT: the same launches over the batch's m and n (A.counts_m / A.counts_n say where each sample
+// ends; the three constants below are then computed per sample on the device).
+template <bool CNT>
 int sinkhorn_run(SkArgs& A, int batch, int iters, hipStream_t st) {
   const int m = A.m, n = A.n;
   // norm = -log(m + n), log_mu = [norm] * m + [log(n) + norm], log_nu likewise (:203-205)
@@ -717,11 +844,12 @@ int sinkhorn_run(SkArgs& A, int batch, int iters, hipStream_t st) {
   // (one chunk: its rows are strided by the waves of a single workgroup per 64 columns)
   const dim3 gcol(ceil_div(n + 1, 64), A.chunks, batch);
   for (int it = 0; it < iters; ++it) {
-    OP_LAUNCH(K_SG_SINKHORN, st, sk_row_kernel, dim3(ceil_div(m + 1, 4), batch), dim3(256), 0, st, A);
-    OP_LAUNCH(K_SG_SINKHORN, st, sk_col_kernel, gcol, dim3(256), 0, st, A);
+    OP_LAUNCH(K_SG_SINKHORN, st, sk_row_kernel<CNT>, dim3(ceil_div(m + 1, 4), batch), dim3(256), 0,
+              st, A);
+    OP_LAUNCH(K_SG_SINKHORN, st, sk_col_kernel<CNT>, gcol, dim3(256), 0, st, A);
     if (A.chunks > 1)
-      OP_LAUNCH(K_SG_SINKHORN, st, sk_colmerge_kernel, dim3(ceil_div(n + 1, 256), batch), dim3(256),
-                0, st, A);
+      OP_LAUNCH(K_SG_SINKHORN, st, sk_colmerge_kernel<CNT>, dim3(ceil_div(n + 1, 256), batch),
+                dim3(256), 0, st, A);
   }
   return ONEPOSE_OK;
 }
@@ -922,9 +1050,17 @@ size_t onepose_log_optimal_transport_workspace_bytes(int batch, int m, int n) {
   return sk_plan(nullptr, batch, m, n).bytes;
 }
 
-int onepose_log_optimal_transport(const float* scores, int64_t scores_bstride, int batch, int m,
-                                  int n, float alpha, int iters, float* out, void* workspace,
-                                  size_t workspace_bytes, void* stream) {
+}  // extern "C"
+
+// The bodies of the entry points that exist with and without counts: CNT = false is the uniform
+// entry (null count / size arrays, the CNT = false kernels), CNT = true the counts entry.
+namespace onepose {
+namespace {
+
+template <bool CNT>
+int lot_entry(const float* scores, int64_t scores_bstride, int batch, int m, int n,
+              const int* counts_m, const int* counts_n, float alpha, int iters, float* out,
+              void* workspace, size_t workspace_bytes, void* stream) {
   clear_error();
   const char* bad = check_shape(batch, m, n);
   OP_REQUIRE(bad == nullptr, "log_optimal_transport: %s", bad);
@@ -950,16 +1086,19 @@ int onepose_log_optimal_transport(const float* scores, int64_t scores_bstride, i
   A.v = p.v;
   A.v_bs = (int64_t)v_stride(n);
   A.part = p.part;
+  A.counts_m = counts_m;
+  A.counts_n = counts_n;
   int rc;
-  if ((rc = sinkhorn_run(A, batch, iters, st)) != ONEPOSE_OK) return rc;
-  OP_LAUNCH(K_SG_SINKHORN, st, sk_finish_row_kernel, dim3(ceil_div(m + 1, 4), batch), dim3(256), 0,
-            st, A, out, static_cast<float*>(nullptr), static_cast<int*>(nullptr));
+  if ((rc = sinkhorn_run<CNT>(A, batch, iters, st)) != ONEPOSE_OK) return rc;
+  OP_LAUNCH(K_SG_SINKHORN, st, sk_finish_row_kernel<CNT>, dim3(ceil_div(m + 1, 4), batch), dim3(256),
+            0, st, A, out, static_cast<float*>(nullptr), static_cast<int*>(nullptr));
   return ONEPOSE_OK;
 }
 
-int onepose_mha_softmax(const float* q, int64_t q_bstride, const float* k, int64_t k_bstride,
-                        const float* v, int64_t v_bstride, int batch, int n, int m, float* out,
-                        int64_t out_bstride, void* stream) {
+template <bool CNT>
+int mha_entry(const float* q, int64_t q_bstride, const float* k, int64_t k_bstride, const float* v,
+              int64_t v_bstride, int batch, int n, int m, const int* counts_q, const int* counts_k,
+              float* out, int64_t out_bstride, void* stream) {
   clear_error();
   const char* bad = check_shape(batch, n, m);
   OP_REQUIRE(bad == nullptr, "mha_softmax: %s", bad);
@@ -975,22 +1114,24 @@ int onepose_mha_softmax(const float* q, int64_t q_bstride, const float* k, int64
   AttnArgs a{};
   a.batch = batch;
   a.p[0] = AttnProb{q, k, v, out, q_bstride, k_bstride, v_bstride, out_bstride,
-                    256, 256, 256, 256, n, m, 0};
-  return attn_launch(a, 1, static_cast<hipStream_t>(stream));
+                    256, 256, 256, 256, n, m, 0, counts_q, counts_k};
+  return attn_launch<CNT>(a, 1, static_cast<hipStream_t>(stream));
 }
 
-int onepose_superglue_match(const void* packed_weights,
-                            const float* desc0, int64_t desc0_bstride,
-                            const float* kpts0, int64_t kpts0_bstride,
-                            const float* scores0, int64_t scores0_bstride,
-                            const float* desc1, int64_t desc1_bstride,
-                            const float* kpts1, int64_t kpts1_bstride,
-                            const float* scores1, int64_t scores1_bstride,
-                            int batch, int n0, int n1, int h0, int w0, int h1, int w1,
-                            int sinkhorn_iters, float match_threshold, int precision,
-                            int64_t* matches0, int64_t* matches1, float* mscores0,
-                            float* mscores1, float* log_assignment, void* workspace,
-                            size_t workspace_bytes, void* stream) {
+template <bool CNT>
+int sg_forward(const void* packed_weights,
+               const float* desc0, int64_t desc0_bstride,
+               const float* kpts0, int64_t kpts0_bstride,
+               const float* scores0, int64_t scores0_bstride,
+               const float* desc1, int64_t desc1_bstride,
+               const float* kpts1, int64_t kpts1_bstride,
+               const float* scores1, int64_t scores1_bstride,
+               int batch, int n0, int n1, int h0, int w0, int h1, int w1,
+               const int* counts0, const int* counts1, const int* hw0, const int* hw1,
+               int sinkhorn_iters, float match_threshold, int precision,
+               int64_t* matches0, int64_t* matches1, float* mscores0,
+               float* mscores1, float* log_assignment, void* workspace,
+               size_t workspace_bytes, void* stream) {
   clear_error();
   if (precision != ONEPOSE_PREC_FP32) {
     set_error("superglue_match: precision %d: this matcher runs in ONEPOSE_PREC_FP32 only", precision);
@@ -1008,6 +1149,16 @@ int onepose_superglue_match(const void* packed_weights,
   OP_REQUIRE(desc0_bstride >= 0 && kpts0_bstride >= 0 && scores0_bstride >= 0 &&
                  desc1_bstride >= 0 && kpts1_bstride >= 0 && scores1_bstride >= 0,
              "superglue_match: negative batch stride");
+  if (CNT) {   // a side shared by the batch has one count, the array's n
+    OP_REQUIRE(counts0 == nullptr ||
+                   (desc0_bstride != 0 && kpts0_bstride != 0 && scores0_bstride != 0),
+               "superglue_match: counts0 with image 0 at batch stride 0 (a shared side has no "
+               "per-sample counts)");
+    OP_REQUIRE(counts1 == nullptr ||
+                   (desc1_bstride != 0 && kpts1_bstride != 0 && scores1_bstride != 0),
+               "superglue_match: counts1 with image 1 at batch stride 0 (a shared side has no "
+               "per-sample counts)");
+  }
   OP_REQUIRE(workspace != nullptr, "superglue_match: null workspace");
   OP_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 255) == 0 &&
                  (reinterpret_cast<uintptr_t>(packed_weights) & 15) == 0,
@@ -1030,6 +1181,8 @@ int onepose_superglue_match(const void* packed_weights,
     const int64_t bs[2][3] = {{desc0_bstride, kpts0_bstride, scores0_bstride},
                               {desc1_bstride, kpts1_bstride, scores1_bstride}};
     const int hw[2][2] = {{h0, w0}, {h1, w1}};
+    const int* cnt[2] = {counts0, counts1};
+    const int* hwp[2] = {hw0, hw1};
     for (int s = 0; s < 2; ++s) {
       SgSideIn& P = ia.p[s];
       P.desc = in[s][0];
@@ -1043,16 +1196,18 @@ int onepose_superglue_match(const void* packed_weights,
       P.cx = w / 2.f;
       P.cy = h / 2.f;
       P.scale = (w > h ? w : h) * 0.7f;
+      P.counts = cnt[s];
+      P.hw = hwp[s];
       P.xd = p.msg[s];   // free until the first attention
       P.h3 = p.y1[s];    // free until the first MLP
     }
     ia.p[0].tiles = ceil_div(n0, 64) * 4;
     ia.p[1].tiles = ceil_div(n1, 64) * 4;
-    OP_LAUNCH(K_SG_INPUT, st, sg_transpose_kernel, dim3((ia.p[0].tiles + ia.p[1].tiles) * B),
+    OP_LAUNCH(K_SG_INPUT, st, sg_transpose_kernel<CNT>, dim3((ia.p[0].tiles + ia.p[1].tiles) * B),
               dim3(256), 0, st, ia);
     ia.p[0].tiles = ceil_div(n0, kKencTok);
     ia.p[1].tiles = ceil_div(n1, kKencTok);
-    OP_LAUNCH(K_SG_INPUT, st, sg_kenc_kernel, dim3((ia.p[0].tiles + ia.p[1].tiles) * B), dim3(128),
+    OP_LAUNCH(K_SG_INPUT, st, sg_kenc_kernel<CNT>, dim3((ia.p[0].tiles + ia.p[1].tiles) * B), dim3(128),
               0, st, ia, wb);
     GemmArgs a;
     a.nprob = 2;   // layer 4: 128 -> 256 (BatchNorm folded), pre-ReLU, into the QKV buffer
@@ -1090,9 +1245,10 @@ int onepose_superglue_match(const void* packed_weights,
       const int src = cross ? 1 - s : s;
       at.p[s] = AttnProb{p.qkv[s], p.qkv[src] + 256, p.qkv[src] + 512, p.msg[s],
                          (int64_t)nn[s] * 768, (int64_t)nn[src] * 768, (int64_t)nn[src] * 768,
-                         (int64_t)nn[s] * 256, 768, 768, 768, 256, nn[s], nn[src], 0};
+                         (int64_t)nn[s] * 256, 768, 768, 768, 256, nn[s], nn[src], 0,
+                         s == 0 ? counts0 : counts1, src == 0 ? counts0 : counts1};
     }
-    if ((rc = attn_launch(at, 2, st)) != ONEPOSE_OK) return rc;
+    if ((rc = attn_launch<CNT>(at, 2, st)) != ONEPOSE_OK) return rc;
     for (int s = 0; s < 2; ++s) {   // MLP conv 1 on cat[x, message]
       GemmProb& g = a.p[s];
       g = gemm_prob(p.x[cur][s], 256, L + kLyW1, 512, L + kLyB1, p.y1[s], 512, nn[s], 512, 512, B);
@@ -1146,15 +1302,93 @@ int onepose_superglue_match(const void* packed_weights,
   A.v = p.v;
   A.v_bs = (int64_t)v_stride(n1);
   A.part = p.part;
-  if ((rc = sinkhorn_run(A, B, sinkhorn_iters, st)) != ONEPOSE_OK) return rc;
-  OP_LAUNCH(K_SG_SINKHORN, st, sk_finish_row_kernel, dim3(ceil_div(n0 + 1, 4), B), dim3(256), 0, st,
-            A, log_assignment, p.rowmax, p.rowidx);
-  OP_LAUNCH(K_SG_MATCH, st, sk_finish_col_kernel, dim3(ceil_div(n1, 64), A.chunks, B), dim3(256), 0,
-            st, A, p.cpart);
-  OP_LAUNCH(K_SG_MATCH, st, sg_mutual_kernel, dim3(B), dim3(1024), 0, st, p.rowmax, p.rowidx,
+  A.counts_m = counts0;
+  A.counts_n = counts1;
+  if ((rc = sinkhorn_run<CNT>(A, B, sinkhorn_iters, st)) != ONEPOSE_OK) return rc;
+  OP_LAUNCH(K_SG_SINKHORN, st, sk_finish_row_kernel<CNT>, dim3(ceil_div(n0 + 1, 4), B), dim3(256), 0,
+            st, A, log_assignment, p.rowmax, p.rowidx);
+  OP_LAUNCH(K_SG_MATCH, st, sk_finish_col_kernel<CNT>, dim3(ceil_div(n1, 64), A.chunks, B), dim3(256),
+            0, st, A, p.cpart);
+  OP_LAUNCH(K_SG_MATCH, st, sg_mutual_kernel<CNT>, dim3(B), dim3(1024), 0, st, p.rowmax, p.rowidx,
             p.cpart, A.chunks, n0, n1, match_threshold, p.colidx, matches0, matches1, mscores0,
-            mscores1);
+            mscores1, counts0, counts1);
   return ONEPOSE_OK;
+}
+
+}  // namespace
+}  // namespace onepose
+
+extern "C" {
+
+int onepose_superglue_counts_version(void) { return 1; }
+
+int onepose_log_optimal_transport(const float* scores, int64_t scores_bstride, int batch, int m,
+                                  int n, float alpha, int iters, float* out, void* workspace,
+                                  size_t workspace_bytes, void* stream) {
+  return lot_entry<false>(scores, scores_bstride, batch, m, n, nullptr, nullptr, alpha, iters, out,
+                          workspace, workspace_bytes, stream);
+}
+
+int onepose_log_optimal_transport_counts(const float* scores, int64_t scores_bstride, int batch,
+                                         int m, int n, const int* counts_m, const int* counts_n,
+                                         float alpha, int iters, float* out, void* workspace,
+                                         size_t workspace_bytes, void* stream) {
+  return lot_entry<true>(scores, scores_bstride, batch, m, n, counts_m, counts_n, alpha, iters, out,
+                         workspace, workspace_bytes, stream);
+}
+
+int onepose_mha_softmax(const float* q, int64_t q_bstride, const float* k, int64_t k_bstride,
+                        const float* v, int64_t v_bstride, int batch, int n, int m, float* out,
+                        int64_t out_bstride, void* stream) {
+  return mha_entry<false>(q, q_bstride, k, k_bstride, v, v_bstride, batch, n, m, nullptr, nullptr,
+                          out, out_bstride, stream);
+}
+
+int onepose_mha_softmax_counts(const float* q, int64_t q_bstride, const float* k, int64_t k_bstride,
+                               const float* v, int64_t v_bstride, int batch, int n, int m,
+                               const int* counts_q, const int* counts_k, float* out,
+                               int64_t out_bstride, void* stream) {
+  return mha_entry<true>(q, q_bstride, k, k_bstride, v, v_bstride, batch, n, m, counts_q, counts_k,
+                         out, out_bstride, stream);
+}
+
+int onepose_superglue_match(const void* packed_weights,
+                            const float* desc0, int64_t desc0_bstride,
+                            const float* kpts0, int64_t kpts0_bstride,
+                            const float* scores0, int64_t scores0_bstride,
+                            const float* desc1, int64_t desc1_bstride,
+                            const float* kpts1, int64_t kpts1_bstride,
+                            const float* scores1, int64_t scores1_bstride,
+                            int batch, int n0, int n1, int h0, int w0, int h1, int w1,
+                            int sinkhorn_iters, float match_threshold, int precision,
+                            int64_t* matches0, int64_t* matches1, float* mscores0,
+                            float* mscores1, float* log_assignment, void* workspace,
+                            size_t workspace_bytes, void* stream) {
+  return sg_forward<false>(packed_weights, desc0, desc0_bstride, kpts0, kpts0_bstride, scores0,
+                           scores0_bstride, desc1, desc1_bstride, kpts1, kpts1_bstride, scores1,
+                           scores1_bstride, batch, n0, n1, h0, w0, h1, w1, nullptr, nullptr, nullptr,
+                           nullptr, sinkhorn_iters, match_threshold, precision, matches0, matches1,
+                           mscores0, mscores1, log_assignment, workspace, workspace_bytes, stream);
+}
+
+int onepose_superglue_match_counts(const void* packed_weights,
+                                   const float* desc0, int64_t desc0_bstride,
+                                   const float* kpts0, int64_t kpts0_bstride,
+                                   const float* scores0, int64_t scores0_bstride,
+                                   const float* desc1, int64_t desc1_bstride,
+                                   const float* kpts1, int64_t kpts1_bstride,
+                                   const float* scores1, int64_t scores1_bstride,
+                                   int batch, int n0, int n1, int h0, int w0, int h1, int w1,
+                                   const int* counts0, const int* counts1, const int* hw0,
+                                   const int* hw1, int sinkhorn_iters, float match_threshold,
+                                   int precision, int64_t* matches0, int64_t* matches1,
+                                   float* mscores0, float* mscores1, float* log_assignment,
+                                   void* workspace, size_t workspace_bytes, void* stream) {
+  return sg_forward<true>(packed_weights, desc0, desc0_bstride, kpts0, kpts0_bstride, scores0,
+                          scores0_bstride, desc1, desc1_bstride, kpts1, kpts1_bstride, scores1,
+                          scores1_bstride, batch, n0, n1, h0, w0, h1, w1, counts0, counts1, hw0, hw1,
+                          sinkhorn_iters, match_threshold, precision, matches0, matches1, mscores0,
+                          mscores1, log_assignment, workspace, workspace_bytes, stream);
 }
 
 }  // extern "C"

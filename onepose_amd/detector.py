@@ -10,6 +10,9 @@ and nothing leaves the device before the result does:
 * the reference views are uploaded once, at construction; views with the same keypoint count
   and image size go through one matcher call with the query shared (batch stride 0), the others
   get a call of their own -- no padding, which would change the attention;
+  ``batch_views="all"`` instead uploads the non-empty views as one group padded to the largest
+  count, with device counts and per-view image sizes, and makes one matcher call per query
+  (the matcher's counts entry keeps the padding out of the attention and the transport);
 * ``detect`` / ``detect_by_matching`` / ``crop_img_by_bbox`` / ``previous_pose_detect`` /
   ``save_detection`` / ``save_K_crop`` keep the reference's signatures and return values;
   ``detect_raw`` returns the device tensors without a host synchronisation of its own;
@@ -192,9 +195,15 @@ def _shape_only(batch, size_hw):
 class LocalFeatureObjectDetector:
     def __init__(self, extractor, matcher, db_dict=None, sfm_ws_dir=None, n_ref_view=15,
                  output_results=False, detect_save_dir=None, K_crop_save_dir=None,
-                 rank_by="reference", device=None):
+                 rank_by="reference", device=None, batch_views="equal"):
         if rank_by not in RANK_MODES:
             raise ValueError(f"rank_by {rank_by!r}: one of {sorted(RANK_MODES)}")
+        if batch_views not in ("equal", "all"):
+            raise ValueError(f"batch_views {batch_views!r}: 'equal' or 'all'")
+        if batch_views == "all" and not getattr(matcher, "supports_counts", False):
+            raise ValueError(f"batch_views='all': {type(matcher).__name__} does not declare "
+                             "supports_counts (padded batches with per-sample counts)")
+        self.batch_views = batch_views
         if db_dict is None:
             if sfm_ws_dir is not None:
                 raise NotImplementedError(
@@ -235,6 +244,27 @@ class LocalFeatureObjectDetector:
             if counts[b] > 0:
                 groups.setdefault((counts[b], int(v["size"][0]), int(v["size"][1])), []).append(b)
         self.groups = []
+        rows = [b for b in range(B) if counts[b] > 0]
+        if self.batch_views == "all" and rows:
+            # one padded group: zeros past a view's count, counts and (h, w) on the device
+            G, n = len(rows), max(counts[b] for b in rows)
+            kp0 = np.zeros((G, n, 2), np.float32)
+            sc0 = np.zeros((G, n), np.float32)
+            de0 = np.zeros((G, 256, n), np.float32)
+            for g, b in enumerate(rows):
+                c = counts[b]
+                kp0[g, :c] = np.asarray(views[b]["keypoints"], np.float32).reshape(c, 2)
+                sc0[g, :c] = np.asarray(views[b]["scores"], np.float32).reshape(c)
+                de0[g, :, :c] = np.asarray(views[b]["descriptors"], np.float32).reshape(256, c)
+            # (_shape_only's quirk, per view: the matcher reads (h, w) = the size reversed)
+            hw = [[int(views[b]["size"][1]), int(views[b]["size"][0])] for b in rows]
+            self.groups.append({
+                "n": n, "rows": torch.tensor(rows, dtype=torch.int64, device=dev),
+                "keypoints0": torch.from_numpy(kp0).to(dev), "scores0": torch.from_numpy(sc0).to(dev),
+                "descriptors0": torch.from_numpy(de0).to(dev),
+                "counts0": torch.tensor([counts[b] for b in rows], dtype=torch.int32, device=dev),
+                "image_hw0": torch.tensor(hw, dtype=torch.int32, device=dev)})
+            return
         for (n, h, w), rows in groups.items():
             f32 = lambda key: torch.from_numpy(np.stack(   # noqa: E731
                 [np.asarray(views[b][key], np.float32) for b in rows])).to(dev)
@@ -265,8 +295,9 @@ class LocalFeatureObjectDetector:
         H, W = int(query_hw[0]), int(query_hw[1])
         for g in self.groups:
             G = g["rows"].shape[0]
-            data = {"keypoints0": g["keypoints0"], "scores0": g["scores0"],
-                    "descriptors0": g["descriptors0"], "image0": g["image0"],
+            data = {k: g[k] for k in ("keypoints0", "scores0", "descriptors0", "image0",
+                                      "counts0", "image_hw0") if k in g}
+            data = {**data,
                     "keypoints1": keypoints[None].expand(G, n1, 2),
                     "scores1": scores[None].expand(G, n1),
                     "descriptors1": descriptors[None].expand(G, 256, n1),

@@ -130,17 +130,123 @@ def names_to_pair(name0, name1):
     return "_".join((name0.replace("/", "-"), name1.replace("/", "-")))
 
 
+def plan_match_batches(counts, batch_size, max_pad_ratio=0.25):
+    """Groups of pair indices for padded matcher calls.  ``counts``: the list of ``(n0, n1)`` of
+    the pairs to match (after the skip rule).  Every pair appears in exactly one group; no group
+    has more than ``batch_size`` pairs; and in every group the padded token count
+    ``B * (max n0 + max n1)`` is at most ``(1 + max_pad_ratio)`` times the group's real token
+    count ``sum(n0 + n1)`` (a pair alone always satisfies this).  Pure Python and deterministic:
+    a stable sort by ``(n0, n1)`` and a greedy walk that closes a group when the next pair would
+    break a cap.  The default of 0.25 is a first guess, not a tuned value."""
+    batch_size = int(batch_size)
+    if batch_size < 1:
+        raise ValueError(f"batch_size {batch_size}: at least 1")
+    if not max_pad_ratio >= 0:
+        raise ValueError(f"max_pad_ratio {max_pad_ratio}: a number >= 0")
+    counts = [(int(a), int(b)) for a, b in counts]
+    order = sorted(range(len(counts)), key=lambda i: counts[i])
+    groups, cur, m0, m1, real = [], [], 0, 0, 0
+    for i in order:
+        n0, n1 = counts[i]
+        if cur:
+            g0, g1, r = max(m0, n0), max(m1, n1), real + n0 + n1
+            if len(cur) < batch_size and (len(cur) + 1) * (g0 + g1) <= (1 + max_pad_ratio) * r:
+                cur.append(i)
+                m0, m1, real = g0, g1, r
+                continue
+            groups.append(cur)
+        cur, m0, m1, real = [i], n0, n1, n0 + n1
+    if cur:
+        groups.append(cur)
+    return groups
+
+
+def _pair_outputs(pred, b, n0, n1):
+    """Sample ``b`` of a matcher's prediction as ``match_pairs`` stores it: trimmed to the pair's
+    own counts, int16 matches and float16 scores."""
+    grp = {"matches0": pred["matches0"][b, :n0].cpu().short().numpy(),
+           "matches1": pred["matches1"][b, :n1].cpu().short().numpy()}
+    for k, n in (("matching_scores0", n0), ("matching_scores1", n1)):
+        if k in pred:
+            grp[k] = pred[k][b, :n].cpu().half().numpy()
+    return grp
+
+
+def _match_group(features, todo, matcher, device):
+    """One padded matcher call over the pairs ``todo`` (``(name0, name1)``, both sides non-empty):
+    every per-keypoint key padded with zeros to the group's maxima, ``counts0/1`` and
+    ``image_hw0/1`` saying where each sample ends and how large its image is."""
+    sides = [[features[p[s]] for p in todo] for s in (0, 1)]
+    data = {}
+    for s, feats in enumerate(sides):
+        ns = [int(np.asarray(f["keypoints"]).reshape(-1, 2).shape[0]) for f in feats]
+        nmax = max(ns)
+        for k in feats[0].keys():
+            if k == "image_size":
+                continue
+            arrs = [np.asarray(f[k], dtype=np.float32) for f in feats]
+            # the keypoint axis: the first for keypoints [n, 2] and scores [n], the last for
+            # descriptors [256, n]
+            axis = arrs[0].ndim - 1 if k == "descriptors" else 0
+            if any(a.ndim == 0 or a.shape[axis] != n for a, n in zip(arrs, ns)):
+                raise ValueError(f"match_pairs: feature key {k!r} has no keypoint axis; batched "
+                                 "matching pads keypoints, scores and descriptors only")
+            shape = list(arrs[0].shape)
+            shape[axis] = nmax
+            buf = np.zeros([len(feats)] + shape, np.float32)
+            for b, (a, n) in enumerate(zip(arrs, ns)):
+                idx = [b] + [slice(None)] * a.ndim
+                idx[1 + axis] = slice(0, n)
+                buf[tuple(idx)] = a
+            data[f"{k}{s}"] = torch.from_numpy(buf).to(device or "cpu")
+        data[f"counts{s}"] = torch.tensor(ns, dtype=torch.int32, device=device or "cpu")
+        # image_size is (w, h)
+        data[f"image_hw{s}"] = torch.tensor(
+            [[int(v) for v in np.asarray(f["image_size"]).reshape(2)[::-1]] for f in feats],
+            dtype=torch.int32, device=device or "cpu")
+        data[f"image_size{s}"] = torch.tensor(
+            np.stack([np.asarray(f["image_size"], np.float32).reshape(-1) for f in feats])
+        ).to(device or "cpu")
+    return matcher(data), data["counts0"].tolist(), data["counts1"].tolist()
+
+
 @torch.no_grad()
-def match_pairs(features, pairs, matcher, device=None):
+def match_pairs(features, pairs, matcher, device=None, batch_size=None, max_pad_ratio=0.25):
     """One matcher call per pair -> ``{pair name: {'matches0' int16, 'matches1' int16,
     'matching_scores0' float16, 'matching_scores1' float16}}``.  A pair is skipped when it or its
     reverse was matched before.  ``features``: ``name -> {key: array}`` with ``image_size`` (w, h)
     among the keys; every key reaches the matcher with the side's suffix, as a float tensor with
-    a batch axis on ``device``."""
-    out, matched = {}, set()
+    a batch axis on ``device``.
+
+    ``batch_size``: None is the loop above.  A number batches the pairs: ``plan_match_batches``
+    groups them (at most ``batch_size`` pairs and ``max_pad_ratio`` of padding per group), each
+    group is one padded matcher call with ``counts0/1`` and ``image_hw0/1``, and every pair's
+    outputs are trimmed to its own counts; the mapping has the same keys in the same order.  The
+    matcher must declare ``supports_counts = True`` (``SuperGlue`` does).  A pair with an empty
+    side never enters a batch and takes the per-pair path."""
+    if batch_size is not None and not getattr(matcher, "supports_counts", False):
+        raise ValueError(f"match_pairs(batch_size={batch_size}): {type(matcher).__name__} does not "
+                         "declare supports_counts (padded batches with per-sample counts)")
+    out, matched, todo = {}, set(), []
     for name0, name1 in pairs:
         pair = names_to_pair(name0, name1)
         if len({(name0, name1), (name1, name0)} & matched) or pair in out:
+            continue
+        out[pair] = None   # (keeps the mapping in pair order)
+        todo.append((name0, name1))
+        matched |= {(name0, name1), (name1, name0)}
+    count = lambda name: int(np.asarray(features[name]["keypoints"]).reshape(-1, 2).shape[0])  # noqa: E731
+    batched = ([p for p in todo if count(p[0]) > 0 and count(p[1]) > 0]
+               if batch_size is not None else [])
+    for group in plan_match_batches([(count(a), count(b)) for a, b in batched], batch_size or 1,
+                                    max_pad_ratio):
+        names = [batched[i] for i in group]
+        pred, ns0, ns1 = _match_group(features, names, matcher, device)
+        for b, (name0, name1) in enumerate(names):
+            out[names_to_pair(name0, name1)] = _pair_outputs(pred, b, ns0[b], ns1[b])
+    for name0, name1 in todo:
+        pair = names_to_pair(name0, name1)
+        if out[pair] is not None:
             continue
         feats0, feats1 = features[name0], features[name1]
         data = {}
@@ -159,7 +265,6 @@ def match_pairs(features, pairs, matcher, device=None):
             if k in pred:
                 grp[k] = pred[k][0].cpu().half().numpy()
         out[pair] = grp
-        matched |= {(name0, name1), (name1, name0)}
     return out
 
 
@@ -895,7 +1000,8 @@ def triangulate_tracks(Rt, K4, track_start, obs_image, obs_xy, max_reproj=MAX_RE
 # ------------------------------------------------------------------ the chain
 def reconstruct(features, img_lists, poses, Ks, matcher, covis_num=10, min_match_score=None,
                 out_dir=None, device=None, seq_ids=None, max_reproj=MAX_REPROJ,
-                min_angle_deg=MIN_ANGLE_DEG, match_device=None, verify=None, verify_options=None):
+                min_angle_deg=MIN_ANGLE_DEG, match_device=None, verify=None, verify_options=None,
+                match_batch=None):
     """Pairs, match export, match import, tracks, triangulation and the compaction of the kept
     tracks.  ``poses``: world-to-camera ``[m, 4, 4]`` (or pose files), ``Ks [m, 3, 3]``, both in
     the order of ``img_lists``; ``features[name]`` holds ``keypoints [n, 2]``, ``image_size``
@@ -903,7 +1009,8 @@ def reconstruct(features, img_lists, poses, Ks, matcher, covis_num=10, min_match
     gets its tensors on ``match_device`` (default: ``device``).  ``verify``: None (no geometric
     verification), ``"estimate"`` or ``"poses"`` -- ``verify_matches`` with that geometry (and
     ``verify_options`` as its keywords) between the match export and the import; its report is
-    the model's ``'two_view'``.
+    the model's ``'two_view'``.  ``match_batch``: ``match_pairs``' ``batch_size`` (None: one
+    matcher call per pair).
 
     Returns one mapping with the keys of ``object_builder.read_points3d_binary`` and
     ``read_images_binary`` (and of ``empty_model``), plus ``'pairs'`` and ``'tracks'``; with
@@ -912,7 +1019,8 @@ def reconstruct(features, img_lists, poses, Ks, matcher, covis_num=10, min_match
     P = _load_poses(poses)
     pairs = covis_from_pose(img_lists, poses, covis_num, seq_ids=seq_ids)
     matches = match_pairs(features, pairs, matcher,
-                          device=device if match_device is None else match_device)
+                          device=device if match_device is None else match_device,
+                          batch_size=match_batch)
     two_view = None
     if verify is not None:
         matches, two_view = verify_matches(pairs, matches, features, geometry=verify, poses=P,

@@ -9,6 +9,11 @@ and shapes (a reference state dict loads with ``strict=True``) and the same
   to the library as shared, not copied;
 * outputs ``matches0/1`` int64 (-1 = unmatched) and ``matching_scores0/1`` float32, whole batch;
 * no keypoints on either side returns the reference's dict with int32 indices (:269-276);
+* optional ``counts0/1 [B]`` (integers: how many leading keypoints of each sample are real) and
+  ``image_hw0/1 [B, 2]`` (per-sample (h, w)): pairs of unequal counts and image sizes in one
+  call, padded to the batch maxima.  The four outputs come back padded: -1 and 0 past a
+  sample's count, and everywhere for a sample with an empty side.  Without these keys the call
+  is what it was;
 * ``GNN_layers`` other than ``['self', 'cross'] * 9`` and a ``descriptor_dim`` other than 256
   raise ``NotImplementedError`` (the kernels are built for that network).
 
@@ -83,6 +88,8 @@ class SuperGlue(nn.Module):
         "sinkhorn_iterations": 100,
         "match_threshold": 0.2,
     }
+    # forward takes counts0/1 and image_hw0/1 (sfm.match_pairs(batch_size=...) asks for this)
+    supports_counts = True
 
     def __init__(self, config=None):
         super().__init__()
@@ -164,6 +171,25 @@ class SuperGlue(nn.Module):
             x = x.contiguous()
         return x, (0 if shared and B > 1 else x[0].numel())
 
+    @staticmethod
+    def _image_hw(data, side):
+        """The scalar (h, w) of a side: ``image{side}``'s shape; with ``image_hw{side}`` given the
+        image may be left out (the scalars are then not read)."""
+        if f"image{side}" in data or f"image_hw{side}" not in data:
+            return data[f"image{side}"].shape[-2:]
+        return 1, 1
+
+    @staticmethod
+    def _int_operand(x, shape, dev, what):
+        """None, or the contiguous int32 device tensor of that shape."""
+        if x is None:
+            return None
+        x = torch.as_tensor(x)
+        if tuple(x.shape) != tuple(shape) or x.is_floating_point():
+            raise ValueError(f"SuperGlue: {what} must be an integer tensor of shape {list(shape)}, "
+                             f"got {x.dtype} {list(x.shape)}")
+        return x.to(device=dev, dtype=torch.int32).contiguous()
+
     def forward(self, data, return_log_assignment=False):
         kpts0, kpts1 = data["keypoints0"], data["keypoints1"]
         if kpts0.shape[1] == 0 or kpts1.shape[1] == 0:   # no keypoints
@@ -188,8 +214,13 @@ class SuperGlue(nn.Module):
         d1, d1s = self._operand(data["descriptors1"], B, (256, n1))
         k1, k1s = self._operand(kpts1, B, (n1, 2))
         s1, s1s = self._operand(data["scores1"], B, (n1,))
-        h0, w0 = data["image0"].shape[-2:]
-        h1, w1 = data["image1"].shape[-2:]
+        h0, w0 = self._image_hw(data, 0)
+        h1, w1 = self._image_hw(data, 1)
+        counted = any(k in data for k in ("counts0", "counts1", "image_hw0", "image_hw1"))
+        if counted:
+            i32 = lambda k, shape: self._int_operand(data.get(k), shape, dev, k)   # noqa: E731
+            extra = dict(counts0=i32("counts0", (B,)), counts1=i32("counts1", (B,)),
+                         hw0=i32("image_hw0", (B, 2)), hw1=i32("image_hw1", (B, 2)))
         with torch.cuda.device(dev):
             w = self.packed_weights(dev)
             ws = self._workspace(dev, B, n0, n1)
@@ -197,9 +228,12 @@ class SuperGlue(nn.Module):
             m1 = torch.empty(B, n1, dtype=torch.int64, device=dev)
             ms0 = torch.empty(B, n0, dtype=torch.float32, device=dev)
             ms1 = torch.empty(B, n1, dtype=torch.float32, device=dev)
-            la = (torch.empty(B, n0 + 1, n1 + 1, dtype=torch.float32, device=dev)
+            # (with counts only each sample's top-left block is written: zeros elsewhere)
+            la = ((torch.zeros if counted else torch.empty)(
+                B, n0 + 1, n1 + 1, dtype=torch.float32, device=dev)
                   if return_log_assignment else None)
-            _lib.run("onepose_superglue_match", packed_weights=w, desc0=d0, desc0_bstride=d0s,
+            _lib.run("onepose_superglue_match_counts" if counted else "onepose_superglue_match",
+                     **(extra if counted else {}), packed_weights=w, desc0=d0, desc0_bstride=d0s,
                      kpts0=k0, kpts0_bstride=k0s, scores0=s0, scores0_bstride=s0s, desc1=d1,
                      desc1_bstride=d1s, kpts1=k1, kpts1_bstride=k1s, scores1=s1,
                      scores1_bstride=s1s, batch=B, n0=n0, n1=n1, h0=int(h0), w0=int(w0),

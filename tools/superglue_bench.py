@@ -161,7 +161,7 @@ def bench_shape(name, B, n0, n1, shared, sd_np, dev, replays, eager_reps):
         for _ in range(5):
             graph.replay()
         torch.cuda.synchronize()
-        hip_ms, _ = median_ms(graph.replay, replays)
+        hip_ms, hip_times = median_ms(graph.replay, replays)
         for _ in range(2):
             eager_forward(sd, d, ITERS, 0.2)
         torch.cuda.synchronize()
@@ -170,6 +170,7 @@ def bench_shape(name, B, n0, n1, shared, sd_np, dev, replays, eager_reps):
     sk_bytes = 2.0 * ITERS * B * (n0 + 1) * (n1 + 1) * 4
     res = {"shape": {"batch": B, "n0": n0, "n1": n1, "side1_shared": shared, "iters": ITERS},
            "hip_graph_ms_median": hip_ms, "hip_replays": replays,
+           "hip_graph_ms_min": float(min(hip_times)), "hip_graph_ms_max": float(max(hip_times)),
            "eager_torch_ms_median": eager_ms, "eager_reps": eager_reps,
            "speedup_vs_eager": eager_ms / hip_ms,
            "indices_equal_eager": same, "max_score_diff_vs_eager": dscore,
