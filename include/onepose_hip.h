@@ -1097,5 +1097,6 @@ const char* onepose_profile_kind_name(int kind);
 /* Families added after ABI 9 keep their declarations and contract in a header of their own. */
 #include "onepose_two_view.h"   /* two-view verification: batched F-matrix RANSAC */
 #include "onepose_superglue_counts.h"   /* SuperGlue batches of unequal counts and image sizes */
+#include "onepose_global_ba.h"   /* global bundle adjustment: Schur-PCG Levenberg-Marquardt */
 
 #endif /* ONEPOSE_HIP_H */

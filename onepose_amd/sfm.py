@@ -25,6 +25,12 @@ The reference's ``sfm_core`` (``run.py:140-193``) after feature extraction, stag
                                  are the connected components of the match graph, and the
                                  triangulator is the one stated in ``include/onepose_hip.h``
                                  ("Sparse reconstruction").  Parity with COLMAP is not verified.
+* ``global_bundle_adjust``    -- the step the reference leaves to COLMAP's ``bundle_adjuster``
+                                 (``src/sfm/global_ba.py``: extrinsics refined, intrinsics
+                                 fixed).  **This project's own**: Levenberg-Marquardt with
+                                 preconditioned CG on the implicit Schur complement, as stated in
+                                 ``include/onepose_global_ba.h`` (``onepose_amd/global_ba.py``).
+                                 Parity with COLMAP or Ceres is not claimed.
 * ``reconstruct``             -- the chain; its result feeds ``object_builder.build_object``.
 
 The host stages are numpy only.  ``verify_matches``, ``build_tracks`` and ``triangulate_tracks``
@@ -32,9 +38,10 @@ take ``device=``: with a GPU device the HIP kernels of ``csrc/two_view.hip`` and
 run; with ``device=None`` the same contract runs on the host.
 
 Out of scope: COLMAP's own verifier (E and H models, LO-RANSAC, cheirality tests, two-view
-geometries written to a database), its RANSAC triangulation and bundle adjustment, point colours,
-the sqlite database, ``model_analyzer`` statistics, PLY export, batching pairs into one matcher
-call.
+geometries written to a database), its RANSAC triangulation, its bundle adjuster's
+parametrisation, robust losses and refinement of intrinsics, filtering or re-triangulating
+points after the adjustment, point colours, the sqlite database, ``model_analyzer`` statistics,
+PLY export, batching pairs into one matcher call.
 """
 from __future__ import annotations
 
@@ -45,6 +52,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from .global_ba import global_bundle_adjust  # noqa: F401  (a stage of this module's chain)
 from .object_builder import _gpu
 
 MIN_ROTATION = 10   # degrees, pairs_from_poses.py:45
@@ -1001,7 +1009,7 @@ def triangulate_tracks(Rt, K4, track_start, obs_image, obs_xy, max_reproj=MAX_RE
 def reconstruct(features, img_lists, poses, Ks, matcher, covis_num=10, min_match_score=None,
                 out_dir=None, device=None, seq_ids=None, max_reproj=MAX_REPROJ,
                 min_angle_deg=MIN_ANGLE_DEG, match_device=None, verify=None, verify_options=None,
-                match_batch=None):
+                match_batch=None, refine=None, refine_options=None):
     """Pairs, match export, match import, tracks, triangulation and the compaction of the kept
     tracks.  ``poses``: world-to-camera ``[m, 4, 4]`` (or pose files), ``Ks [m, 3, 3]``, both in
     the order of ``img_lists``; ``features[name]`` holds ``keypoints [n, 2]``, ``image_size``
@@ -1010,11 +1018,16 @@ def reconstruct(features, img_lists, poses, Ks, matcher, covis_num=10, min_match
     verification), ``"estimate"`` or ``"poses"`` -- ``verify_matches`` with that geometry (and
     ``verify_options`` as its keywords) between the match export and the import; its report is
     the model's ``'two_view'``.  ``match_batch``: ``match_pairs``' ``batch_size`` (None: one
-    matcher call per pair).
+    matcher call per pair).  ``refine``: None (the input poses are taken as exact) or
+    ``"global_ba"`` -- ``global_bundle_adjust`` on the triangulated model (``refine_options`` as
+    its keywords, on ``device``); the refined model is what is returned and written, and its
+    ``'global_ba'`` holds the solver's report.
 
     Returns one mapping with the keys of ``object_builder.read_points3d_binary`` and
     ``read_images_binary`` (and of ``empty_model``), plus ``'pairs'`` and ``'tracks'``; with
     ``out_dir`` the three ``.bin`` files are written there as well."""
+    if refine not in (None, "global_ba"):
+        raise ValueError(f"reconstruct: refine={refine!r}; expected None or 'global_ba'")
     img_lists = list(img_lists)
     P = _load_poses(poses)
     pairs = covis_from_pose(img_lists, poses, covis_num, seq_ids=seq_ids)
@@ -1065,6 +1078,8 @@ def reconstruct(features, img_lists, poses, Ks, matcher, covis_num=10, min_match
     })
     if two_view is not None:
         model["two_view"] = two_view
+    if refine is not None:
+        model = global_bundle_adjust(model, device=device, **(refine_options or {}))
     if out_dir is not None:
         write_model_binary(model, out_dir)
     return model
