@@ -1,5 +1,6 @@
-"""Seeded inputs of the sparse-reconstruction tests, shared by tests/golden/make_golden_sfm.py
-and the test files so that both see the same bytes (the generator records a hash)."""
+"""Seeded inputs of the sparse-reconstruction tests, shared by tests/golden/make_golden_sfm.py,
+tests/golden/make_golden_sfm_edges.py and the test files so that all see the same bytes (the
+generators record a hash)."""
 import hashlib
 import os
 
@@ -48,6 +49,38 @@ def graph_cases():
     oor = path_graph(100, "random", seed=9)
     bad = np.array([[-1, 4], [4, 100], [2**31 - 1, 0], [-2**31, -2**31], [50, -7]], np.int32)
     cases["out_of_range"] = (np.concatenate([oor[:50], bad, oor[50:]]), 100)
+    cases.update(large_graph_cases())
+    return cases
+
+
+LARGE_GRAPHS = ("star2000_hub_last", "star2000_hub0", "complete40", "grid64_shuffled",
+                "sparse65537", "two_paths500_joined")
+SPARSE_NODES, SPARSE_EDGES = 65537, 60000
+
+
+def large_graph_cases():
+    """Graphs with a hub, a dense graph, more nodes than a few blocks: name -> (edges, n_nodes).
+    star2000_hub_last / _hub0: 2000 leaves around the highest / the lowest id (every edge of one
+    launch hooks the same root, or every root hooks node 0); complete40: every ordered pair;
+    grid64_shuffled: a 64 x 64 grid under a permutation of the ids; sparse65537: 60 000 random
+    edges over 65 537 nodes (a giant component, thousands of small ones, isolated nodes);
+    two_paths500_joined: two random-order paths whose joining edge is the last of the list."""
+    cases = {}
+    leaves = np.arange(2000)
+    cases["star2000_hub_last"] = (np.stack([leaves, np.full(2000, 2000)], 1).astype(np.int32), 2001)
+    cases["star2000_hub0"] = (np.stack([np.zeros(2000, np.int64), leaves + 1], 1).astype(np.int32),
+                              2001)
+    u, v = np.nonzero(~np.eye(40, dtype=bool))
+    cases["complete40"] = (np.stack([u, v], 1).astype(np.int32), 40)
+    ids = np.random.default_rng(64).permutation(64 * 64).reshape(64, 64)
+    cases["grid64_shuffled"] = (np.concatenate(
+        [np.stack([ids[:, :-1].ravel(), ids[:, 1:].ravel()], 1),
+         np.stack([ids[:-1].ravel(), ids[1:].ravel()], 1)]).astype(np.int32), 64 * 64)
+    cases["sparse65537"] = (np.random.default_rng(65537).integers(
+        0, SPARSE_NODES, (SPARSE_EDGES, 2)).astype(np.int32), SPARSE_NODES)
+    a, b = path_graph(500, "random", seed=500), path_graph(500, "random", seed=501) + 500
+    cases["two_paths500_joined"] = (np.concatenate(
+        [a, b, np.array([[a[-1, 1], b[0, 0]]], np.int32)]).astype(np.int32), 1000)
     return cases
 
 
@@ -152,6 +185,165 @@ def tri_problem(seed=4100):
 
 def tri_sha(p):
     return sha(*[p[k] for k in sorted(p)])
+
+
+# ---- the edge cases of the triangulation ------------------------------------------------------
+EDGE_NAMES = ("drop_past_64", "dup_past_64", "dup_exact_tie", "empty_mid", "behind_two",
+              "final_check_drop", "noise_free", "mostly_unrelated", "same_centre", "same_ray",
+              "parallel_rays", "empty_last")
+EDGE_KEPT = ("drop_past_64", "dup_past_64", "dup_exact_tie", "behind_two", "final_check_drop",
+             "noise_free")   # reason 0 by construction, compared in bits
+EDGE_DEGENERATE = ("same_centre", "same_ray", "parallel_rays")   # the Jacobi oracle's decisions only
+EDGE_DROPS = {"drop_past_64": (3, 64, 67, 130, 199), "behind_two": (1, 70)}
+EDGE_TIES = ((2, 6), (3, 67), (10, 70))   # dup_exact_tie: (the original, its byte copy)
+EDGE_DUPS = ((5, 69), (10, 100, 139))   # dup_past_64: positions that share an image
+FINAL_CHECK_SEED = 370   # make_golden_sfm_edges.py --search: the widest margin below 600
+EDGE_AWAY, EDGE_SAME_CENTRE, EDGE_COPY_OF, EDGE_COPY = (260, 261), (262, 263), 7, 264
+EDGE_PARALLEL = (265, 266)
+UNRELATED_SEED = 19   # of 40 tried: two observations survive 62 drops, the widest margin
+
+
+def final_check_track(seed, Rt, K4):
+    """4 observations of one point, 0.5 px noise, one shifted by 3.6 .. 4.6 px in a random
+    direction -> (cams, uv [4, 2]).  Seeded on its own: the search for a seed at which the shifted
+    observation passes at the DLT point and fails at the refined one changes nothing else."""
+    rng = np.random.default_rng(seed)
+    cams = rng.permutation(TRI_CAMERAS)[:4]
+    X = rng.uniform(-0.1, 0.1, 3)
+    uv = np.stack([project(Rt[c], K4[c], X) for c in cams]) + 0.5 * rng.standard_normal((4, 2))
+    a = rng.uniform(0, 2 * np.pi)
+    uv[rng.integers(0, 4)] += rng.uniform(3.6, 4.6) * np.array([np.cos(a), np.sin(a)])
+    return cams, uv
+
+
+def edge_problem(seed=4300, final_check_seed=None, unrelated_seed=None):
+    """A second CSR beside tri_problem(), tracks in EDGE_NAMES order.  Cameras 0..259 are
+    tri_problem()'s band; 260 and 261 look away from the object (every point is behind them); 262
+    and 263 share a centre and differ in orientation; 264 is camera 7 again under another id; 265
+    and 266 have R = I and centres 0.1 m apart, and parallel_rays gives both their principal
+    point: the rows' third entries are exact zeros, the Jacobi's vector is (0, 0, 1, 0) and
+    X = h[0:3] / h[3] is (NaN, NaN, inf)."""
+    rng = np.random.default_rng(seed)
+    Rt, K4 = ring_cameras(TRI_CAMERAS, 4100)
+    centre = (0.0, -0.5, 0.1)
+    extra = [look_at((0.5, 0.0, 0.0), target=(1.0, 0.0, 0.05)),
+             look_at((0.0, 0.5, 0.1), target=(0.05, 1.0, 0.1)),
+             look_at(centre), look_at(centre, target=(0.06, 0.0, 0.03)), Rt[EDGE_COPY_OF],
+             np.concatenate([np.eye(3), [[0.0], [0.0], [0.5]]], 1),
+             np.concatenate([np.eye(3), [[0.1], [0.0], [0.5]]], 1)]
+    Rt = np.concatenate([Rt, np.stack(extra)])
+    K4 = np.concatenate([K4, np.tile([[F, F, C, C]], (4, 1)), K4[EDGE_COPY_OF][None],
+                         np.tile([[F, F, C, C]], (2, 1))])
+    start, img, xy = [0], [], []
+
+    def track(cams, X, noise=0.5, shift=None):
+        for k, c in enumerate(cams):
+            uv = project(Rt[c], K4[c], X) + noise * rng.standard_normal(2)
+            if shift is not None and k in shift:
+                uv = uv + shift[k]
+            img.append(int(c))
+            xy.append(uv)
+        start.append(len(img))
+
+    def point():
+        return rng.uniform(-0.1, 0.1, 3)
+
+    def gross(lo=30.0, hi=110.0):
+        a = rng.uniform(0, 2 * np.pi)
+        return rng.uniform(lo, hi) * np.array([np.cos(a), np.sin(a)])
+    # drop_past_64
+    track(rng.permutation(TRI_CAMERAS)[:200], point(),
+          shift={p: gross() for p in EDGE_DROPS["drop_past_64"]})
+    # dup_past_64: 5 and 69 fall in one lane, 10, 100 and 139 in three
+    cams = rng.permutation(TRI_CAMERAS)[:140]
+    for first, *rest in EDGE_DUPS:
+        cams[rest] = cams[first]
+    track(cams, point())
+    # dup_exact_tie: byte copies, image id and pixel
+    base = len(img)
+    track(rng.permutation(TRI_CAMERAS)[:80], point())
+    for src, dst in EDGE_TIES:
+        img[base + dst], xy[base + dst] = img[base + src], xy[base + src].copy()
+    start.append(len(img))   # empty_mid
+    # behind_two: the projection formula gives a pixel with a small residual at a negative depth
+    cams = rng.permutation(TRI_CAMERAS)[:80]
+    cams[list(EDGE_DROPS["behind_two"])] = EDGE_AWAY
+    track(cams, point())
+    # final_check_drop
+    cams, uv = final_check_track(FINAL_CHECK_SEED if final_check_seed is None else final_check_seed,
+                                 Rt, K4)
+    img.extend(int(c) for c in cams)
+    xy.extend(uv)
+    start.append(len(img))
+    # noise_free
+    track(rng.permutation(TRI_CAMERAS)[:9], point(), noise=0.0)
+    # mostly_unrelated: positions 2..63 are uniform random pixels
+    base = len(img)
+    track(rng.permutation(TRI_CAMERAS)[:64], point())
+    unrelated = np.random.default_rng(UNRELATED_SEED if unrelated_seed is None else unrelated_seed)
+    for p in range(2, 64):
+        xy[base + p] = unrelated.uniform(10.0, 502.0, 2)
+    track(EDGE_SAME_CENTRE, point(), noise=0.0)
+    uv = project(Rt[EDGE_COPY_OF], K4[EDGE_COPY_OF], point())   # same_ray
+    img.extend([EDGE_COPY_OF, EDGE_COPY])
+    xy.extend([uv, uv.copy()])
+    start.append(len(img))
+    img.extend(EDGE_PARALLEL)   # parallel_rays
+    xy.extend([np.array([C, C]), np.array([C, C])])
+    start.append(len(img))
+    start.append(len(img))   # empty_last: start == n_obs
+    assert len(start) - 1 == len(EDGE_NAMES)
+    return {"Rt": Rt, "K4": K4, "track_start": np.asarray(start, np.int32),
+            "obs_image": np.asarray(img, np.int32), "obs_xy": np.asarray(xy, np.float64)}
+
+
+BIG_TRACKS = 3000
+
+
+def big_csr(seed=4400):
+    """3000 tracks of 0, 2 or 3 observations (about one in fifty empty) over the band's cameras,
+    0.5 px noise: more tracks than two strides of the CSR check and more observations than four."""
+    rng = np.random.default_rng(seed)
+    Rt, K4 = ring_cameras(TRI_CAMERAS, 4100)
+    start, img, xy = [0], [], []
+    for t in range(BIG_TRACKS):
+        n = 0 if rng.random() < 0.02 else int(rng.integers(2, 4))
+        X = rng.uniform(-0.1, 0.1, 3)
+        for c in rng.permutation(TRI_CAMERAS)[:n]:
+            img.append(int(c))
+            xy.append(project(Rt[c], K4[c], X) + 0.5 * rng.standard_normal(2))
+        start.append(len(img))
+    p = {"Rt": Rt, "K4": K4, "track_start": np.asarray(start, np.int32),
+         "obs_image": np.asarray(img, np.int32), "obs_xy": np.asarray(xy, np.float64)}
+    assert len(img) > 4600 and (np.diff(p["track_start"]) == 0).sum() > 20
+    return p
+
+
+def malformed_csrs(p):
+    """name -> (track_start, obs_image, the (status, index) the header's sentence gives): one
+    offender in the last slot of the check's first stride, in the first of its second, in its
+    last trip; two offenders in different trips; both kinds at once."""
+    T, n_img = len(p["track_start"]) - 1, len(p["Rt"])
+    out = {}
+
+    def case(name, starts=(), images=(), want=None):
+        ts, img = p["track_start"].copy(), p["obs_image"].copy()
+        for t in starts:
+            ts[t] = ts[t - 1] - 1   # below its predecessor; its successor stays above it
+        for k, o in enumerate(images):
+            img[o] = n_img if k % 2 == 0 else -1
+        out[name] = (ts, img, want)
+    case("start_1023", starts=(1023,), want=(1, 1023))
+    case("start_1024", starts=(1024,), want=(1, 1024))
+    case("start_last_track", starts=(T - 1,), want=(1, T - 1))
+    case("starts_1500_2600", starts=(1500, 2600), want=(1, 1500))
+    case("image_4095", images=(4095,), want=(2, 4095))
+    case("images_4500_1030", images=(4500, 1030), want=(2, 1030))
+    case("start_2000_image_5", starts=(2000,), images=(5,), want=(1, 2000))
+    ts = p["track_start"].copy()
+    ts[T] -= 1   # the end entry: the loop's last index, t == n_tracks
+    out["end_entry"] = (ts, p["obs_image"].copy(), (1, T))
+    return out
 
 
 # ---- the chain's scene ----------------------------------------------------------------------

@@ -104,12 +104,12 @@ def _project(Rt, K, X, uv):
     return p, ru, rv
 
 
-def _error(Rt, K, X, uv):
+def _error(Rt, K, X, uv, depth=True):
     p, ru, rv = _project(Rt, K, X, uv)
     e = math.sqrt(ru * ru + rv * rv) if math.isfinite(ru * ru + rv * rv) else float(ru * ru + rv * rv)
     if math.isnan(e) or math.isnan(p[2]):
         return float("nan")
-    return e if p[2] > 0 else float("inf")
+    return e if p[2] > 0 or not depth else float("inf")
 
 
 def _note(margins, value):
@@ -117,11 +117,43 @@ def _note(margins, value):
         margins.append(abs(value))
 
 
+def check_csr(track_start, obs_image, n_images, variant=None):
+    """The check that runs before anything is read through the CSR -> (status, index): status 1
+    when track_start is not 0 = s[0] <= s[1] <= ... <= s[n_tracks] = n_obs, else 2 when an image
+    id lies outside [0, n_images), else 0; index is the smallest offending index (0 when clean).
+    ``variant`` breaks one rule on purpose for tests/test_sfm_model_host.py."""
+    s, img = [int(v) for v in track_start], [int(v) for v in obs_image]
+    n_tracks, n_obs = len(s) - 1, len(img)
+    starts, images = [], []
+    for t in range(n_tracks + 1):
+        bad = s[t] < 0 or s[t] > n_obs
+        if t == 0 and s[t] != 0:
+            bad = True
+        if t == n_tracks and s[t] != n_obs:
+            bad = True
+        if t > 0 and s[t] < s[t - 1]:
+            bad = True
+        if bad:
+            starts.append(t)
+    for o in range(n_obs):
+        if img[o] < 0 or img[o] >= n_images:
+            images.append(o)
+    pick = max if variant == "first offender found" else min   # found scanning from the end
+    order = [(1, starts), (2, images)]
+    if variant == "image ids before starts":
+        order.reverse()
+    for status, found in order:
+        if found:
+            return status, pick(found)
+    return 0, 0
+
+
 def triangulate(Rt, K4, img, uv, max_reproj, min_angle_deg, solver="jacobi", variant=None,
-                margins=None):
+                margins=None, ties=None):
     """-> (reason, X [3] or None, err or None, keep [len] bool).  ``margins`` collects the
     distance of every decision from its threshold (px or degrees) and of every tie-break from a
-    tie."""
+    tie; ``ties`` collects the position pairs (stays, leaves) of the duplicate rule whose errors
+    are equal."""
     Rt, K4 = np.asarray(Rt, np.float64), np.asarray(K4, np.float64)
     img, uv = [int(i) for i in img], np.asarray(uv, np.float64).reshape(-1, 2)
     L = len(img)
@@ -163,7 +195,8 @@ def triangulate(Rt, K4, img, uv, max_reproj, min_angle_deg, solver="jacobi", var
         return X if np.isfinite(X).all() else None
 
     def errors(X):
-        return [_error(Rt[img[p]], K4[img[p]], X, uv[p]) if S[p] else None for p in range(L)]
+        return [_error(Rt[img[p]], K4[img[p]], X, uv[p], variant != "depth not tested")
+                if S[p] else None for p in range(L)]
 
     # 1, 2
     while True:
@@ -177,9 +210,11 @@ def triangulate(Rt, K4, img, uv, max_reproj, min_angle_deg, solver="jacobi", var
         for p in range(L):
             if S[p]:
                 _note(margins, e[p] - max_reproj)
+                if variant == "worst among the first 64 positions" and p >= 64:
+                    continue
                 if worst is None or e[p] > e[worst]:
                     worst = p
-        if not e[worst] > max_reproj or variant == "no drop-worst loop":
+        if worst is None or not e[worst] > max_reproj or variant == "no drop-worst loop":
             break
         for p in range(L):
             if S[p] and p != worst and e[p] > max_reproj:
@@ -201,7 +236,10 @@ def triangulate(Rt, K4, img, uv, max_reproj, min_angle_deg, solver="jacobi", var
                 q = best.get(img[p])
                 if q is not None:
                     _note(margins, e[p] - e[q])
-                if q is None or e[p] < e[q]:
+                    if ties is not None and e[p] == e[q]:
+                        ties.append((q, p))
+                if q is None or e[p] < e[q] or (
+                        variant == "duplicate ties to the highest position" and e[p] == e[q]):
                     best[img[p]] = p
         for p in range(L):
             if S[p] and best[img[p]] != p:
@@ -260,7 +298,7 @@ def triangulate(Rt, K4, img, uv, max_reproj, min_angle_deg, solver="jacobi", var
     for p in range(L):
         if S[p]:
             _note(margins, e[p] - max_reproj)
-            if not e[p] <= max_reproj:
+            if not e[p] <= max_reproj and variant != "no final check":
                 S[p] = False
     if sum(S) < 2:
         return 1, None, None, keep

@@ -86,7 +86,8 @@ def test_components_replay_in_a_graph(lib, device):
 
 
 def test_wrapper_and_build_tracks_equal_the_host(device):
-    for name in ("path1025_random", "duplicates", "out_of_range", "empty65"):
+    for name in ("path1025_random", "duplicates", "out_of_range", "empty65", "star2000_hub_last",
+                 "grid64_shuffled", "sparse65537"):
         edges, n = GRAPHS[name]
         counts = [n // 3, n - n // 3 - n // 4, n // 4]
         a = sfm.build_tracks(counts, edges, device=device)

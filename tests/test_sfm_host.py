@@ -254,6 +254,109 @@ def test_host_triangulation_refuses_a_malformed_csr():
         sfm.triangulate_tracks(p["Rt"], p["K4"], p["track_start"], img, p["obs_xy"])
 
 
+# ---- the edge fixture and the CSR larger than one stride of the check ---------------------------
+EDGES = golden("sfm_tri_edges")
+KEYS = ("xyz", "err", "reason", "n_kept", "obs_keep")
+
+
+def _generator():
+    import sys
+    if C.GOLDEN not in sys.path:
+        sys.path.insert(0, C.GOLDEN)
+    import make_golden_sfm_edges as G
+    return G
+
+
+def _same(out, prefix, keys=KEYS):
+    """Decisions equal, xyz and err equal in bits on the kept tracks and NaN on the others."""
+    kept = EDGES[f"{prefix}_reason"] == 0
+    for k in keys:
+        want = EDGES[f"{prefix}_{k}"]
+        assert out[k].dtype == want.dtype, k
+        if k in ("xyz", "err"):
+            assert out[k][kept].tobytes() == want[kept].tobytes(), (prefix, k)
+            assert np.isnan(out[k][~kept]).all(), (prefix, k)
+        else:
+            assert np.array_equal(out[k], want), (prefix, k)
+
+
+def test_the_edge_fixture_equals_the_oracle_run_afresh():
+    G = _generator()
+    p = C.edge_problem()
+    assert C.tri_sha(p) == str(EDGES["edge_sha"])
+    assert int(EDGES["edge_final_check_seed"]) == C.FINAL_CHECK_SEED
+    assert float(EDGES["edge_margin"]) >= 1e-6
+    out, margins, ties = G.run(p)
+    _same(out, "edge")
+    t = C.EDGE_NAMES.index("dup_exact_tie")
+    assert sorted(ties[t]) == sorted(C.EDGE_TIES) and not any(ties[:t] + ties[t + 1:])
+    assert sorted(margins[t])[:4][:3] == [0.0] * 3 and sorted(margins[t])[3] >= 1e-6
+    rest = [m for k, ms in enumerate(margins) for m in ms if k != t or m != 0.0]
+    assert min(rest) == float(EDGES["edge_margin"])
+    _same(G.run(p, max_reproj=np.inf)[0], "inf")
+    assert np.array_equal(G.run(p, max_reproj=0.0)[0]["reason"], EDGES["zero_reason"])
+    kept = EDGES["edge_reason"] == 0
+    assert np.isfinite(EDGES["edge_tol"][kept]).all() and np.isfinite(EDGES["edge_ls_dist"][kept]).all()
+
+
+def test_the_big_csr_fixture_equals_the_oracle_run_afresh():
+    p = C.big_csr()
+    assert C.tri_sha(p) == str(EDGES["big_sha"]) and float(EDGES["big_margin"]) >= 1e-6
+    _same(_generator().run(p)[0], "big")
+    assert O.check_csr(p["track_start"], p["obs_image"], len(p["Rt"])) == (0, 0)
+    for name, (ts, img, want) in C.malformed_csrs(p).items():
+        assert O.check_csr(ts, img, len(p["Rt"])) == want, name
+        with pytest.raises(sfm._lib.OnePoseError, match="monotone" if want[0] == 1 else "image id"):
+            sfm.triangulate_tracks(p["Rt"], p["K4"], ts, img, p["obs_xy"])
+
+
+def test_host_triangulation_equals_the_edge_fixtures():
+    """sfm.triangulate_tracks(device=None) on both new problems and at both thresholds: the
+    oracle's decisions, and its xyz and err bit for bit."""
+    p = C.edge_problem()
+    args = (p["Rt"], p["K4"], p["track_start"], p["obs_image"], p["obs_xy"])
+    _same(sfm.triangulate_tracks(*args), "edge")
+    _same(sfm.triangulate_tracks(*args, max_reproj=np.inf), "inf")
+    assert np.array_equal(sfm.triangulate_tracks(*args, max_reproj=0.0)["reason"], EDGES["zero_reason"])
+    b = C.big_csr()
+    _same(sfm.triangulate_tracks(b["Rt"], b["K4"], b["track_start"], b["obs_image"], b["obs_xy"]), "big")
+
+
+REFUSALS = [   # (entry point, the arguments changed, the header's message)
+    ("tri", dict(n_tracks=0), "tracks_triangulate: n_tracks=0 outside 1..2^24"),
+    ("tri", dict(n_obs=0), "tracks_triangulate: n_obs=0 outside 1..2^28"),
+    ("tri", dict(n_images=0), "tracks_triangulate: n_images=0"),
+    ("tri", dict(max_reproj=float("nan")), "tracks_triangulate: NaN threshold"),
+    ("tri", dict(min_angle_deg=float("nan")), "tracks_triangulate: NaN threshold"),
+    ("tri", dict(obs_keep=None), "tracks_triangulate: null pointer"),
+    ("tri", dict(status=None), "tracks_triangulate: null pointer"),
+    ("cc", dict(n_nodes=0), "track_components: n_nodes=0 outside 1..2^30"),
+    ("cc", dict(rounds=65), "track_components: rounds=65 outside 0..64"),
+    ("cc", dict(n_edges=-1), "track_components: n_edges=-1 outside 0..2^30"),
+    ("cc", dict(parent=None), "track_components: null pointer"),
+]
+
+
+@pytest.mark.parametrize("entry,change,text", REFUSALS,
+                         ids=[f"{e}-{'-'.join(c)}" for e, c, _ in REFUSALS])
+def test_host_refusals_launch_nothing(entry, change, text):
+    """Every pointer is a value that is never dereferenced: the call is refused on the host
+    before a launch, with code 1 (ONEPOSE_ERR_INVALID) and the message of the check."""
+    lib = sfm._lib.load()
+    p = 0x1000
+    if entry == "tri":
+        a = dict(Rt=p, K4=p, n_images=3, track_start=p, obs_image=p, obs_xy=p, n_tracks=2, n_obs=5,
+                 max_reproj=4.0, min_angle_deg=1.5, xyz=p, err=p, reason=p, n_kept=p, obs_keep=p,
+                 status=p, stream=None)
+        a.update(change)
+        rc = lib.onepose_tracks_triangulate(*a.values())
+    else:
+        a = dict(edges=p, n_edges=4, n_nodes=8, rounds=2, init=1, parent=p, status=p, stream=None)
+        a.update(change)
+        rc = lib.onepose_track_components(*a.values())
+    assert rc == 1 and lib.onepose_last_error().decode() == text
+
+
 # ---- the chain on the host ----------------------------------------------------------------------
 class OracleNN:
     """NearestNeighbour's forward dict from tests/nn_oracle.py (numpy), for the host chain."""

@@ -65,3 +65,72 @@ def test_a_wrong_rule_misses_a_bar(variant):
         assert same and ratio >= MARGIN
     else:
         assert same and not bits
+
+
+# ---- the edge fixture's bars (tests/golden/make_golden_sfm_edges.py) ------------------------------
+EDGES = golden("sfm_tri_edges")
+
+# variant -> (the track of edge_problem() that separates it, what it gets wrong there)
+EDGE_VARIANTS = {
+    "duplicate ties to the highest position": ("dup_exact_tie", "kept set: the byte copies at 6, "
+                                               "67 and 70 stay instead of 2, 3 and 10"),
+    "no final check": ("final_check_drop", "kept set: the observation that fails at the refined "
+                                           "point stays"),
+    "depth not tested": ("behind_two", "kept set: the two observations behind their cameras "
+                                       "have small residuals and stay"),
+    "worst among the first 64 positions": ("drop_past_64", "xyz: the gross errors at 64, 67, 130 "
+                                           "and 199 are never the worst, stay through the solves "
+                                           "and the refinement and leave only at the final check"),
+}
+
+
+def _edge_bars(variant, t):
+    p = C.edge_problem()
+    a, b = p["track_start"][t], p["track_start"][t + 1]
+    why, X, err, keep = O.triangulate(p["Rt"], p["K4"], p["obs_image"][a:b], p["obs_xy"][a:b],
+                                      C.MAX_REPROJ, C.MIN_ANGLE, variant=variant)
+    want = EDGES["edge_obs_keep"][a:b]
+    same = (why == EDGES["edge_reason"][t] and (keep.sum() if why == 0 else 0) == EDGES["edge_n_kept"][t]
+            and np.array_equal(keep if why == 0 else np.zeros(b - a, bool), want))
+    if not same or why != 0:
+        return same, same, np.nan, keep, want
+    bits = (np.asarray(X).tobytes() == EDGES["edge_xyz"][t].tobytes()
+            and np.float64(err).tobytes() == EDGES["edge_err"][t].tobytes())
+    dev = max(np.abs(X - EDGES["edge_xyz"][t]).max(), abs(err - EDGES["edge_err"][t]))
+    return same, bits, dev / EDGES["edge_tol"][t], keep, want
+
+
+def test_the_oracle_meets_every_edge_bar():
+    for t, name in enumerate(C.EDGE_NAMES):
+        same, bits, ratio, _, _ = _edge_bars(None, t)
+        assert same and bits and not ratio > 0, name
+
+
+@pytest.mark.parametrize("variant", list(EDGE_VARIANTS))
+def test_a_wrong_rule_misses_an_edge_bar(variant):
+    case, what = EDGE_VARIANTS[variant]
+    same, bits, ratio, keep, want = _edge_bars(variant, C.EDGE_NAMES.index(case))
+    differ = np.nonzero(keep != want)[0].tolist()
+    print(f"{variant} on {case}: decisions equal {same}, obs_keep differs at positions {differ}, "
+          f"deviation {ratio:.3g} x the tolerance, bits equal {bits} ({what})")
+    if what.startswith("kept set"):
+        assert not same and differ
+    else:
+        assert same and not bits and ratio >= MARGIN
+
+
+# variant of check_csr -> (the malformed CSR that separates it, what it reports there)
+CSR_VARIANTS = {"first offender found": ("starts_1500_2600", (1, 2600)),
+                "image ids before starts": ("start_2000_image_5", (2, 5))}
+
+
+def test_the_csr_check_meets_its_bars_and_its_wrong_variants_miss_them():
+    p = C.big_csr()
+    cases = C.malformed_csrs(p)
+    for name, (ts, img, want) in cases.items():
+        assert O.check_csr(ts, img, len(p["Rt"])) == want, name
+    for variant, (name, wrong) in CSR_VARIANTS.items():
+        ts, img, want = cases[name]
+        got = O.check_csr(ts, img, len(p["Rt"]), variant=variant)
+        print(f"{variant} on {name}: {got}, the header's sentence gives {want}")
+        assert got == wrong != want

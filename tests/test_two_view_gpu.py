@@ -87,6 +87,64 @@ def test_estimate_equals_the_oracle(key, outs, batches):
     assert not out["F"][none].any() and not out["n_inliers"][none].any()
 
 
+# ---- the options and the given-F edges (tests/golden/make_golden_two_view_options.py) ------------
+OPT = golden("two_view_options")
+OPTION_CALLS = C.option_calls()
+
+
+@pytest.mark.parametrize("key", list(OPTION_CALLS))
+def test_option_calls_equal_the_oracle(key, device):
+    """Every call of the "options" family as test_estimate_equals_the_oracle compares a batch:
+    status, count, iterations and mask equal, F within the tolerance recorded with the family,
+    F bit-equal; a given F comes back byte for byte, a NaN entry included."""
+    call = OPTION_CALLS[key]
+    assert C.option_sha(call) == str(OPT[f"{key}_sha"]), key
+    out = verify(device, call, F_in=call.get("F_in"))
+    want = {k: OPT[f"{key}_{k}"] for k in ("F", "mask", "n_inliers", "iters", "status")}
+    assert out["rc"] == 0
+    with np.errstate(invalid="ignore"):
+        dev = np.abs(O.normalised(out["F"]) - O.normalised(want["F"])).max(1)
+    finite = np.isfinite(want["F"]).all(1)
+    bits = sum(out["F"][b].tobytes() == want["F"][b].tobytes() for b in range(len(dev)))
+    print(f"{key}: status {out['status'].tolist()}, inliers {out['n_inliers'].tolist()}, iterations "
+          f"{out['iters'].tolist()}; largest F deviation {dev[finite].max():.3e} (tolerance "
+          f"{float(OPT['f_tol']):.1e}); F bit-equal on {bits} of {len(dev)} pairs")
+    for k in ("status", "n_inliers", "iters"):
+        assert np.array_equal(out[k], want[k]), (k, out[k], want[k])
+    assert np.array_equal(out["mask"], want["mask"])
+    for b, n in enumerate(call["n"]):
+        assert not out["mask"][b, n:].any()   # zero past the count
+    assert (dev[finite] <= float(OPT["f_tol"])).all(), dev
+    assert bits == len(dev)
+    if "F_in" in call:
+        assert out["F"].tobytes() == call["F_in"].tobytes() and not out["iters"].any()
+    else:
+        none = np.isin(out["status"], (1, 2))
+        assert not out["F"][none].any() and not out["n_inliers"][none].any()
+
+
+def test_the_option_calls_hold_what_they_are_for(device):
+    """Spot assertions, so that a fixture recorded again cannot change what a call is for."""
+    def run(key):
+        return verify(device, OPTION_CALLS[key], F_in=OPTION_CALLS[key].get("F_in"))
+    r = {k: run(f"tight_refine{k}") for k in C.REFINE_ITERS}
+    d01, d12, ended = (int(b) for b in OPT["refine_pairs"])
+    assert r[0]["F"][d01].tobytes() != r[1]["F"][d01].tobytes()
+    assert r[1]["F"][d12].tobytes() != r[2]["F"][d12].tobytes()
+    assert r[2]["F"][ended].tobytes() == r[5]["F"][ended].tobytes()   # a refit not kept ends them
+    zero = run("max_error0")
+    assert (zero["status"] == 2).all() and (zero["iters"] == 300).all()
+    tight = np.concatenate([run("max_error0.5")["status"], run("max_error1")["status"]])
+    assert (tight == 3).any() and (tight == 0).any()
+    lo, hi = run("confidence0.5")["iters"], run("confidence0.999999")["iters"]
+    assert lo[0] < 64 and (hi[1:] > 128).all() and (lo[1:] < hi[1:]).all()
+    assert run("ratio0.8")["status"].tolist() == run("ratio1")["status"].tolist() == [0, 3, 3]
+    assert run("ratio-1")["status"].tolist() == [0, 0, 0]
+    for P, counts in C.LDS_MAX_POINTS.items():
+        assert run(f"points{P}")["status"].tolist() == [1 if c < 8 else 0 for c in counts]
+    assert run("given")["status"].tolist() == [3, 3, 3, 1, 1, 1, 1, 0]
+
+
 def test_the_batches_hold_what_they_are_for(outs, batches):
     main, capped = outs["main"], outs["capped"]
     name = {key: list(batches[key]["names"]) for key in batches}

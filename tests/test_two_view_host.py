@@ -89,6 +89,34 @@ def test_device_none_equals_the_oracle(key):
     assert F2.tobytes() == GOLD[f"{key}_F"].tobytes()
 
 
+# ---- the options and the given-F edges ------------------------------------------------------------
+OPT = golden("two_view_options")
+OPTION_CALLS = C.option_calls()
+FIELDS = ("F", "mask", "n_inliers", "iters", "status")
+
+
+@pytest.mark.parametrize("key", list(OPTION_CALLS))
+def test_the_option_fixture_equals_the_oracle_and_the_host_path(key):
+    """two_view_options.npz against the oracle run afresh, and the package's host path against
+    both: decisions equal and F bit for bit, a given F with a NaN entry included."""
+    sys.path.insert(0, GOLDEN)
+    import make_golden_two_view_options as G
+    call = OPTION_CALLS[key]
+    assert list(OPT["calls"]) == list(OPTION_CALLS)
+    assert C.option_sha(call) == str(OPT[f"{key}_sha"]) and list(OPT[f"{key}_names"]) == call["names"]
+    got = G.run_call(call)
+    host = dict(zip(FIELDS, sfm._host_two_view(call["pts0"], call["pts1"], call["counts"],
+                                               call.get("F_in"), **call["options"])))
+    for k in FIELDS:
+        want = OPT[f"{key}_{k}"]
+        assert got[k].dtype == want.dtype and got[k].tobytes() == want.tobytes(), (key, k)
+        assert host[k].dtype == want.dtype and host[k].tobytes() == want.tobytes(), (key, k)
+    if "F_in" in call:
+        assert host["F"].tobytes() == call["F_in"].tobytes()
+    assert float(OPT["f_tol"]) == max(16 * float(OPT["f_dev"]), 1e-12)
+    assert int(OPT["f_same"]) >= 0.75 * int(OPT["f_models"])
+
+
 def test_device_none_equals_the_oracle_on_the_known_answers(host_scenes):
     scenes, want = host_scenes
     P = max(len(s["pts0"]) for s in scenes)

@@ -60,3 +60,33 @@ def test_a_wrong_rule_misses_a_bar(variant, main_batch):
         assert same and ratio >= MARGIN
     else:
         assert same and ratio <= 1.0 and not bits
+
+
+# ---- the option fixtures' bar (tests/golden/make_golden_two_view_options.py) ----------------------
+OPT = golden("two_view_options")
+
+
+def _refit_bars(variant):
+    """(decisions equal, F bits equal, inlier count) on the pair of tight_refine5 that the
+    generator recorded: its refit after the RANSAC model is not kept, which ends the refits."""
+    call = C.option_calls()["tight_refine5"]
+    b = int(OPT["refine_pairs"][2])
+    n = int(call["n"][b])
+    r = O.verify(call["pts0"][b, :n], call["pts1"][b, :n], variant=variant, **call["options"])
+    same = (r["status"] == OPT["tight_refine5_status"][b] and r["iters"] == OPT["tight_refine5_iters"][b]
+            and r["n_inliers"] == OPT["tight_refine5_n_inliers"][b]
+            and np.array_equal(r["mask"], OPT["tight_refine5_mask"][b, :n].astype(bool)))
+    return call["names"][b], same, r["F"].tobytes() == OPT["tight_refine5_F"][b].tobytes(), r["n_inliers"]
+
+
+def test_refits_that_never_stop_miss_the_option_bar():
+    """At refine_iters = 5 with max_error = 0.7 px the recorded pair keeps its RANSAC model: the
+    first refit has fewer inliers and ends the refits.  Going on from the inliers of the refit that
+    was not kept reaches another model, another mask and another F."""
+    assert O.OPTION_VARIANTS == ("refits_never_stop",)
+    name, same, bits, nin = _refit_bars(None)
+    assert same and bits
+    name, same, bits, other = _refit_bars("refits_never_stop")
+    print(f"refits_never_stop on tight_refine5/{name}: decisions equal {same}, F bits equal {bits}, "
+          f"{other} inliers where the contract keeps {nin}")
+    assert not same and not bits

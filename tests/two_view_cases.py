@@ -165,6 +165,83 @@ def gpu_batches(max_points):
     return out
 
 
+# ---- the options and the given-F edges ----------------------------------------------------------
+REFINE_ITERS = (0, 1, 2, 5)
+REFINE_SCENES = ((65, 0.3, 8118), (40, 0.0, 8109), (130, 0.3, 8100), (65, 0.3, 8101))
+TIGHT = dict(max_error=0.7, max_trials=300)   # the noise is +-0.7 px: matches sit at the threshold
+LDS_MAX_POINTS = {8: (8, 5, 7), 9: (9, 4, 8), 15: (15, 6, 11), 17: (17, 7, 12), 33: (33, 3, 20)}
+
+
+def _pack(options, max_points, pairs, F_in=None):
+    B = len(pairs)
+    p0 = np.zeros((B, max_points, 2), np.float32)
+    p1 = np.zeros((B, max_points, 2), np.float32)
+    counts = np.zeros(B, np.int32)
+    for b, (_, a0, a1) in enumerate(pairs):
+        p0[b, :len(a0)], p1[b, :len(a1)], counts[b] = a0, a1, len(a0)
+    out = {"options": options, "max_points": max_points, "names": [p[0] for p in pairs],
+           "pts0": p0, "pts1": p1, "counts": counts, "n": counts.copy()}
+    if F_in is not None:
+        out["F_in"] = np.ascontiguousarray(F_in, np.float64).reshape(B, 9)
+    return out
+
+
+def option_sha(call):
+    """The hash a call is recorded under: its points, counts, given F and options."""
+    arrays = [call["pts0"], call["pts1"], call["counts"]] + ([call["F_in"]] if "F_in" in call else [])
+    return sha(*arrays, np.array(sorted(call["options"].items()), dtype="U32"))
+
+
+def option_calls():
+    """The "options" family: small calls, each with its own options -> name -> the dict of
+    gpu_batches() (plus F_in [B, 9] for the given-geometry call).
+    refine{k}, tight_refine{k}: refine_iters = 0, 1, 2, 5 on one batch, at the defaults and with
+      max_error = 0.7 px, where refits move the mask and one is not kept;
+    max_error{e}: 0, 0.5, 1 and 16 px with max_trials = 300;
+    confidence{c}: 0.5 and 0.999999 on a clean pair (the loop ends inside its first round of 64)
+      and on pairs with 30 % outliers (several rounds at 0.999999);
+    ratio{r}: min_inlier_ratio 0.8, 1.0 and -1 on 30 % outliers and on a clean pair;
+    points{P}: max_points = 8, 9, 15, 17, 33 (the flags start at byte 16 P of the dynamic LDS, whose
+      size 17 P is rounded up to 16) with three pairs of unequal counts, one below
+      min_num_inliers = 8;
+    given: F_in with a NaN entry, an inf entry, all zeros, each also on a pair below
+      min_num_inliers, and a true F."""
+    def pairs(specs):
+        return [(f"n{n}_out{int(100 * share)}_s{seed}", s["pts0"], s["pts1"])
+                for n, share, seed in specs for s in [scene(n, share, seed)]]
+    calls = {}
+    refine = pairs(REFINE_SCENES)
+    P = max(len(p[1]) for p in refine)
+    for k in REFINE_ITERS:
+        calls[f"refine{k}"] = _pack(dict(DEFAULTS, refine_iters=k), P, refine)
+        calls[f"tight_refine{k}"] = _pack(dict(DEFAULTS, refine_iters=k, **TIGHT), P, refine)
+    mixed = pairs(((40, 0.0, 8200), (65, 0.3, 8201), (130, 0.3, 8202), (100, 0.5, 8203)))
+    for e in (0.0, 0.5, 1.0, 16.0):
+        calls[f"max_error{e:g}"] = _pack(dict(DEFAULTS, max_error=e, max_trials=300), 130, mixed)
+    for c in (0.5, 0.999999):
+        calls[f"confidence{c:g}"] = _pack(dict(DEFAULTS, confidence=c), 130, mixed[:3])
+    for r in (0.8, 1.0, -1.0):
+        calls[f"ratio{r:g}"] = _pack(dict(DEFAULTS, min_inlier_ratio=r), 130, mixed[:3])
+    for P, counts in LDS_MAX_POINTS.items():
+        calls[f"points{P}"] = _pack(dict(DEFAULTS, min_num_inliers=8, max_trials=300), P,
+                                    pairs([(c, 0.0, 8301 + 10 * P + j) for j, c in enumerate(counts)]))
+    s, few = scene(40, 0.1, 8400), scene(10, 0.0, 8401)
+    bad = []
+    for k, value in ((4, np.nan), (7, np.inf), (None, 0.0)):
+        Fb = s["F_true"].reshape(9).copy()
+        if k is None:
+            Fb[:] = value
+        else:
+            Fb[k] = value
+        bad.append(Fb)
+    given = ([(f"{name}_n40", s["pts0"], s["pts1"]) for name in ("nan", "inf", "zero")]
+             + [(f"{name}_n10", few["pts0"], few["pts1"]) for name in ("nan", "inf", "zero", "true")]
+             + [("true_n40", s["pts0"], s["pts1"])])
+    calls["given"] = _pack(dict(DEFAULTS), 40, given,
+                           F_in=bad + bad + [few["F_true"].reshape(9), s["F_true"].reshape(9)])
+    return calls
+
+
 # ---- the chain with wrong matches ---------------------------------------------------------------
 class OracleNN:
     """NearestNeighbour's forward dict from tests/nn_oracle.py (numpy), for the host chain."""

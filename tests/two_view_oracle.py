@@ -18,6 +18,11 @@ DBL_MIN = float(np.finfo(np.float64).tiny)
 SQRT2 = 1.4142135623730951
 SWEEPS = 24
 VARIANTS = ("no_hartley", "no_rank2", "algebraic", "no_refit", "reverse_sums")
+# "refits_never_stop": a refit that is not kept does not end the refits.  Retried on the unchanged
+# inliers it would only repeat itself (the same list gives the same F' and the same verdict), so
+# the variant is the way such a loop goes wrong in practice: the next refit runs on the inliers of
+# the candidate that was not kept.  Held by the option fixtures (test_two_view_model_host.py).
+OPTION_VARIANTS = ("refits_never_stop",)
 
 
 class CvRng:
@@ -237,15 +242,19 @@ def verify(pts0, pts1, F_in=None, max_error=4.0, confidence=0.999, max_trials=10
         it += 1
     if max_good <= 0:
         return result(2, [0.0] * 9, np.zeros(n, bool), it)
+    current = best_mask   # the inliers a refit runs on: the kept model's
     for _ in range(0 if variant == "no_refit" else refine_iters):
-        order = [i for i in range(n) if best_mask[i]]
+        order = [i for i in range(n) if current[i]]
         if variant == "reverse_sums":
             order = order[::-1]
         F = solve(P, order, variant)
         mask = inliers(F, Q, thr2, variant)
         if not (all(math.isfinite(v) for v in F) and int(mask.sum()) >= int(best_mask.sum())):
+            if variant == "refits_never_stop" and int(mask.sum()) >= 8:
+                current = mask
+                continue
             break
-        best, best_mask = F, mask
+        best, best_mask, current = F, mask, mask
     return decide(best, best_mask, it)
 
 
