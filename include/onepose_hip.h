@@ -1098,5 +1098,6 @@ const char* onepose_profile_kind_name(int kind);
 #include "onepose_two_view.h"   /* two-view verification: batched F-matrix RANSAC */
 #include "onepose_superglue_counts.h"   /* SuperGlue batches of unequal counts and image sizes */
 #include "onepose_global_ba.h"   /* global bundle adjustment: Schur-PCG Levenberg-Marquardt */
+#include "onepose_match_counts.h"   /* the 2D-3D matcher with per-sample keypoint counts */
 
 #endif /* ONEPOSE_HIP_H */

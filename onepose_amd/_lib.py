@@ -25,7 +25,7 @@ HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "onepose_hip.h")
 FAMILY_HEADERS = ("onepose_two_view.h",)
 # Later families: one table per header in FAMILIES ({header: signatures}), so that the tables
 # above stay what they were when their tests pinned them.
-LATER_HEADERS = ("onepose_superglue_counts.h", "onepose_global_ba.h")
+LATER_HEADERS = ("onepose_superglue_counts.h", "onepose_match_counts.h", "onepose_global_ba.h")
 
 c_int, c_int64, c_size_t, c_float, c_double = (ctypes.c_int, ctypes.c_int64, ctypes.c_size_t,
                                                ctypes.c_float, ctypes.c_double)

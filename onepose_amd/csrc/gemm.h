@@ -27,7 +27,22 @@ enum GemmEpi {
                    //   (tile = mt * ntiles + nt): a PRO_HEADZ launch's acc0
   EPI_BIAS_L2 = 6, // y = (acc + bias) / max(|row|_2, 1e-12): the final projection with
                    //   F.normalize fused (tiles hold whole 256-column rows)
+  // Per-sample row counts (GemmProb::counts / ns_counts, include/onepose_match_counts.h): the
+  // epilogue of the same name whose reductions over rows stop at the sample's count.  gemm_launch
+  // picks them when a problem of the launch carries counts; callers pass the plain epilogue.
+  EPI_QKV_CNT = 7,    // KV_h / sum phi(k) partials over rows < count, v / count
+  EPI_STATS_CNT = 8,  // InstanceNorm partials and merges over rows < count (PRO_HEADZ: ns_counts)
+  EPI_SCORE_CNT = 9,  // column (max, sum exp) partials over rows < count
 };
+// the epilogue a counts epilogue restates (itself for the others)
+constexpr int gemm_epi_base(int epi) {
+  return epi == EPI_QKV_CNT ? EPI_QKV : epi == EPI_STATS_CNT ? EPI_STATS
+         : epi == EPI_SCORE_CNT ? EPI_SCORE : epi;
+}
+constexpr int gemm_epi_counts(int epi) {
+  return epi == EPI_QKV ? EPI_QKV_CNT : epi == EPI_STATS ? EPI_STATS_CNT
+         : epi == EPI_SCORE ? EPI_SCORE_CNT : epi;
+}
 enum GemmPro {
   PRO_PLAIN = 0,
   PRO_NORM_RELU = 1,  // a = max((a - mean[k]) * rstd[k], 0)                    (norm + ReLU)
@@ -105,6 +120,12 @@ struct GemmProb {
   float scale;         // EPI_SCORE divisor (scale_factor)
   float vdiv;          // EPI_QKV: v divisor (source length)
   float ns;            // PRO_HEADZ: source length (v_length)
+  // Counts epilogues: [batch] int32 device arrays or null.  counts: the sample's valid rows of
+  // this problem (clamped to [0, M]): every reduction over rows stops there, EPI_QKV's v divisor
+  // is the count, and row tiles past it still store, arrive at the finalize's counters and
+  // contribute nothing.  ns_counts: PRO_HEADZ's source length per sample (clamped to [0, ns]).
+  const int* counts;
+  const int* ns_counts;
   int M, N, K, batch;
   int mtiles, ntiles, tiles;   // filled by gemm_launch
 };
@@ -189,6 +210,12 @@ constexpr GemmVariant kGemmVariants[] = {
     {EPI_BIAS, PRO_PLAIN, TILE_64x64, PM_F32, false, 0},
     {EPI_BIAS_L2, PRO_PLAIN, TILE_32x256W8, PM_F32, false, 0},
     {EPI_ACC, PRO_PLAIN, TILE_64x64, PM_F32, false, 0},
+    // fp32 with per-sample row counts (onepose_match_cached_counts)
+    {EPI_QKV_CNT, PRO_PLAIN, TILE_32x128, PM_F32, false, 0},
+    {EPI_QKV_CNT, PRO_PLAIN, TILE_128x128W8, PM_F32, false, 0},
+    {EPI_QKV_CNT, PRO_PLAIN, TILE_128x128, PM_F32, false, 0},
+    {EPI_STATS_CNT, PRO_HEADZ, TILE_64x64, PM_F32, false, 0},
+    {EPI_SCORE_CNT, PRO_PLAIN, TILE_128x64W8, PM_F32, false, 0},
     // bf16 attention layers: W from the packed bf16 planes (weights rounded on the host, Mf by
     // the KV fold), A from the producers' activation planes (DMA 2) or rounded as the stage is
     // stored

@@ -278,9 +278,13 @@ __device__ __forceinline__ void store_stage(float* base, Stage<T, WPL, NPL>& s) 
 
 // DMA: 0 = register-staged loop; 1 = the lean loop, W planes by global_load_lds and A through
 // registers; 2 = the lean loop with A from activation planes by global_load_lds as well.
-template <int EPI, int PRO, class T, int PM, bool WPL, int DMA = 0>
+template <int EPI_, int PRO, class T, int PM, bool WPL, int DMA = 0>
 __device__ __forceinline__ void gemm_body(const GemmArgs& args, StampTick& tk, StampLds* sl,
                                           int vtile = -1) {
+  // a counts epilogue (gemm.h) is its base epilogue with CNT set: where CNT is false every
+  // statement below is the one the base epilogue always had
+  constexpr int EPI = gemm_epi_base(EPI_);
+  constexpr bool CNT = EPI_ != EPI;
   constexpr int BM = T::BM, BN = T::BN, FN = T::FN, PITCH = T::PITCH;
   constexpr bool BF = PM != PM_F32;   // bf16 LDS images and MFMAs
   constexpr int NPL = PM == PM_SPLIT3 ? 3 : 1;   // bf16 images per operand
@@ -340,6 +344,17 @@ __device__ __forceinline__ void gemm_body(const GemmArgs& args, StampTick& tk, S
   c.M = F(M);
   c.N = F(N);
   c.K = F(K);
+  // valid rows of the sample (CNT: its count, clamped) and PRO_HEADZ's source length
+  int Mv = c.M;
+  float nsv = F(ns);
+  bool has_cnt = false;
+  if constexpr (CNT) {
+    const int* cp = F(counts);
+    const int* np = F(ns_counts);
+    has_cnt = cp != nullptr;
+    if (cp != nullptr) Mv = min(max(cp[b], 0), c.M);
+    if (np != nullptr) nsv = (float)min(max(np[b], 0), (int)nsv);
+  }
   // second K range: its own weights, or the same matrix continuing past ksplit
   c.w1 = w1 ? w1 + b * F(w1_bs) : c.w0 + c.ksplit;
   c.ldw1 = w1 ? F(ldw1) : c.ldw0;
@@ -502,7 +517,7 @@ __device__ __forceinline__ void gemm_body(const GemmArgs& args, StampTick& tk, S
   __shared__ float zks[(PRO == PRO_HEADZ) ? 256 : 1];   // sum phi(k) of the source
   if (PRO == PRO_HEADZ)
     for (int i = t; i < 256; i += T::NT) zks[i] = F(ksum)[b * F(ksum_bs) + i];   // 1st barrier
-  const float zns = F(ns);
+  const float zns = nsv;
   auto zdot = [&](const float* buf, int sg) __attribute__((always_inline)) {
     if (PRO == PRO_HEADZ && sg >= xs && sg < nk) {
 #pragma unroll
@@ -868,6 +883,9 @@ __device__ __forceinline__ void gemm_body(const GemmArgs& args, StampTick& tk, S
     return;
   }
   const int rows = min(BM, M - m0);
+  // the tile's rows below the sample's count (CNT; 0 for a tile wholly past it).  Such rows are
+  // computed and stored like any other and left out of every reduction over rows.
+  const int rows_v = CNT ? max(min(rows, Mv - m0), 0) : rows;
   if constexpr (EPI == EPI_QKV) {
     // 128-column tiles of [q (256) | k_0 v_0 | .. | k_3 v_3].  q tiles: phi(q) = elu(q) + 1,
     // stored by float4 rows.  [k_h | v_h] tiles: phi(k) and v / vdiv staged transposed,
@@ -889,14 +907,16 @@ __device__ __forceinline__ void gemm_body(const GemmArgs& args, StampTick& tk, S
       const float bias = bias_pre[j];   // (n0 + col < N = 768 on every QKV tile)
       // v / vdiv: for a power-of-two source length the product with its reciprocal is the
       // same number (exact scaling), without the division's instruction sequence
-      const float vdiv = F(vdiv), vrcp = 1.0f / vdiv;
+      // (CNT: the source length is the sample's count; an empty sample's v rows are all masked)
+      const float vdiv = has_cnt ? (float)max(Mv, 1) : F(vdiv), vrcp = 1.0f / vdiv;
+      const int mq = q_tile ? M : Mv;   // [k_h | v_h] tiles: rows past the count hold 0
       const bool vpow2 = __builtin_amdgcn_frexp_mant(vdiv) == 0.5f;
       float yv[16];
       auto fill = [&](auto f) __attribute__((always_inline)) {
 #pragma unroll
         for (int i = 0; i < 16; ++i) {
           const int gm = m0 + wm * 32 + (i & 3) + 8 * (i >> 2) + 4 * (lane >> 5);
-          yv[i] = gm < M ? f(acc[j][i] + bias) : 0.f;
+          yv[i] = gm < mq ? f(acc[j][i] + bias) : 0.f;
         }
       };
       // (the column kind is uniform over the wave's 32-column accumulator block)
@@ -1011,7 +1031,14 @@ __device__ __forceinline__ void gemm_body(const GemmArgs& args, StampTick& tk, S
       if (EPI == EPI_STATS) {
         // the column's (mean, M2) over this wave's 32 rows, from the registers: each lane's 16
         // rows, then the lane pair (lane, lane ^ 32) added in the same order on both lanes
-        const int cw = max(min(rows - wm * 32, 32), 0);   // valid rows of the wave's block
+        const int cw = max(min(rows_v - wm * 32, 32), 0);   // valid rows of the wave's block
+        if constexpr (CNT) {   // rows past the count: stored above, 0 in the sums
+#pragma unroll
+          for (int i = 0; i < 16; ++i) {
+            const int row = wm * 32 + (i & 3) + 8 * (i >> 2) + 4 * (lane >> 5);
+            yv[i] = row < rows_v ? yv[i] : 0.f;
+          }
+        }
         float su = 0.f;
 #pragma unroll
         for (int i = 0; i < 16; ++i) su += yv[i];          // invalid rows hold 0
@@ -1023,7 +1050,7 @@ __device__ __forceinline__ void gemm_body(const GemmArgs& args, StampTick& tk, S
         for (int i = 0; i < 16; ++i) {
           const int row = wm * 32 + (i & 3) + 8 * (i >> 2) + 4 * (lane >> 5);
           const float d = yv[i] - wmean;
-          m2 += (row < rows) ? d * d : 0.f;
+          m2 += (row < rows_v) ? d * d : 0.f;
         }
         const float mo = __shfl_xor(m2, 32, 64);
         if (lane < 32) {
@@ -1113,7 +1140,7 @@ __device__ __forceinline__ void gemm_body(const GemmArgs& args, StampTick& tk, S
     if (t < NSUB * BN && n0 + tc < N && ts * SUB < rows) {
       float n = 0.f, mean = 0.f, M2 = 0.f;
       for (int g = ts * NRG; g < ts * NRG + NRG; ++g) {
-        const float nb = (float)max(min(g * RG + RG, rows) - g * RG, 0);
+        const float nb = (float)max(min(g * RG + RG, rows_v) - g * RG, 0);
         if (nb == 0.f) continue;
         const float mb = part[(g * BN + tc) * 2], m2b = part[(g * BN + tc) * 2 + 1];
         in_merge_block(n, mean, M2, nb, mb, m2b);
@@ -1195,15 +1222,20 @@ __device__ __forceinline__ void gemm_body(const GemmArgs& args, StampTick& tk, S
             }
 #pragma unroll
             for (int u = 0; u < UD; ++u) {
-              if (u0 + u < gsz)
-                in_merge_tile(s1, s2, ng, (double)min(SUB, M - (gt0 + u0 + u) * SUB), mv[u], qv[u], c);
+              // (CNT: a tile without a valid row -- partials (0, 0) -- is left out)
+              const int nbt = max(min(SUB, Mv - (gt0 + u0 + u) * SUB), 0);
+              if (u0 + u < gsz && (!CNT || nbt > 0))
+                in_merge_tile(s1, s2, ng, (double)nbt, mv[u], qv[u], c);
             }
           }
           if (n0 + t < N) {
-            __hip_atomic_store(gp + (int64_t)g1 * 2 * N + n0 + t, in_group_mean(c, s1, ng),
-                               __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            __hip_atomic_store(gp + (int64_t)g1 * 2 * N + N + n0 + t, in_group_m2(s1, s2, ng),
-                               __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            const bool some = !CNT || ng > 0.0;   // (CNT: a group past the count stores (0, 0))
+            __hip_atomic_store(gp + (int64_t)g1 * 2 * N + n0 + t,
+                               some ? in_group_mean(c, s1, ng) : 0.0, __ATOMIC_RELAXED,
+                               __HIP_MEMORY_SCOPE_AGENT);
+            __hip_atomic_store(gp + (int64_t)g1 * 2 * N + N + n0 + t,
+                               some ? in_group_m2(s1, s2, ng) : 0.0, __ATOMIC_RELAXED,
+                               __HIP_MEMORY_SCOPE_AGENT);
           }
           asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         }
@@ -1235,13 +1267,16 @@ __device__ __forceinline__ void gemm_body(const GemmArgs& args, StampTick& tk, S
 #pragma unroll
             for (int u = 0; u < GD; ++u) {
               const int g = q0 + u;
-              if (g < ngroups)
-                in_merge_group(S1, S2, (double)min(G * SUB, M - g * G * SUB), mg[u], m2g[u], c);
+              const int ngr = max(min(G * SUB, Mv - g * G * SUB), 0);
+              if (g < ngroups && (!CNT || ngr > 0))
+                in_merge_group(S1, S2, (double)ngr, mg[u], m2g[u], c);
             }
           }
-          const double n = (double)M;
-          F(st_mean)[(int64_t)b * N + n0 + t] = in_final_mean(c, S1, n);
-          F(st_rstd)[(int64_t)b * N + n0 + t] = in_final_rstd(S1, S2, n);
+          const double n = (double)Mv;
+          // (CNT: an empty sample has no statistics; its rows are all padding)
+          const bool some = !CNT || Mv > 0;
+          F(st_mean)[(int64_t)b * N + n0 + t] = some ? in_final_mean(c, S1, n) : 0.f;
+          F(st_rstd)[(int64_t)b * N + n0 + t] = some ? in_final_rstd(S1, S2, n) : 0.f;
         }
       }
     }
@@ -1312,7 +1347,7 @@ __device__ __forceinline__ void gemm_body(const GemmArgs& args, StampTick& tk, S
       }
     }
     if (line < BN) {   // column `line` over this tile's rows
-      const float2 r = partial(tile + line, TP, rows, lo_c, std::integral_constant<int, BM / 4>());
+      const float2 r = partial(tile + line, TP, rows_v, lo_c, std::integral_constant<int, BM / 4>());
       if (qtr == 0 && line < cols) {
         float* o = F(colstat) + (((int64_t)b * mtiles + mt) * N + n0 + line) * 2;
         o[0] = r.x;
@@ -1476,7 +1511,13 @@ int gemm_launch(int epi, int pro, int tile, GemmArgs& args, hipStream_t stream, 
              "gemm: A planes: QKV / MLP conv 1 on the DMA loop (bf16 modes, W planes)");
   OP_REQUIRE(!yplanes || (pm != PM_F32 && (epi == EPI_RESID || epi == EPI_QKV)),
              "gemm: output planes are written by RESID / QKV launches in the bf16 modes");
-  const GemmVariant want = {epi, pro, tile, pm, wpl, wpl ? (adma ? 2 : dma ? 1 : 0) : 0};
+  // per-sample counts on any problem: the epilogue's counts form
+  bool cnt = false;
+  for (int i = 0; i < args.nprob; ++i)
+    cnt = cnt || args.p[i].counts != nullptr || args.p[i].ns_counts != nullptr;
+  OP_REQUIRE(!cnt || gemm_epi_counts(epi) != epi, "gemm: epilogue %d takes no counts", epi);
+  const GemmVariant want = {cnt ? gemm_epi_counts(epi) : epi, pro, tile, pm, wpl,
+                            wpl ? (adma ? 2 : dma ? 1 : 0) : 0};
   if (gemm_has_variant(want)) {
     prof_pre(kind, stream);
     args.stamp = prof_stamp_slot(kind);

@@ -108,6 +108,9 @@ struct TransProb {
   float* dst;
   uint16_t* dstp = nullptr;   // bf16 modes: dst's activation planes ([B][3][n][256]; npl of them)
   int f16 = 0;
+  // transpose_in_counts_kernel: [B] int32 device counts (clamped to [0, n]) or null; a sample's
+  // tokens past its count are written as zero rows whatever the input holds there
+  const int* counts = nullptr;
 };
 struct TransArgs {
   TransProb p[2];
@@ -123,7 +126,8 @@ struct TransArgs {
   CacheHdr expect{};
   unsigned* err = nullptr;
 };
-__global__ __launch_bounds__(256) void transpose_in_kernel(TransArgs args, int batch) {
+template <bool CNT>
+__device__ __forceinline__ void transpose_in_body(const TransArgs& args, int batch) {
   __shared__ float tile[64][65];
   if (blockIdx.x == 0 && threadIdx.x == 0 && args.err != nullptr) {
     unsigned bad = 0u;
@@ -187,16 +191,28 @@ __global__ __launch_bounds__(256) void transpose_in_kernel(TransArgs args, int b
   __syncthreads();
   float* d = P.dst + (int64_t)b * n * kDim;
   uint16_t* dp = P.dstp != nullptr ? P.dstp + (int64_t)b * kPlanesMax * n * kDim : nullptr;
+  int cn = n;   // the sample's count
+  if constexpr (CNT) {
+    if (P.counts != nullptr) cn = min(max(P.counts[b], 0), n);
+  }
 #pragma unroll
   for (int i = 0; i < 4; ++i) {   // 64 tokens x 16 float4 of channels
     const int e = t + 256 * i, tk = e >> 4, cq = (e & 15) * 4;
     if (n0 + tk < n) {
-      const float4 v = make_float4(tile[cq][tk], tile[cq + 1][tk], tile[cq + 2][tk], tile[cq + 3][tk]);
+      float4 v = make_float4(tile[cq][tk], tile[cq + 1][tk], tile[cq + 2][tk], tile[cq + 3][tk]);
+      if (CNT && n0 + tk >= cn) v = make_float4(0.f, 0.f, 0.f, 0.f);   // (a select: NaN stays out)
       *reinterpret_cast<float4*>(d + (int64_t)(n0 + tk) * kDim + c0 + cq) = v;
       if (dp != nullptr)
         store_planes4(dp + (int64_t)(n0 + tk) * kDim + c0 + cq, (int64_t)n * kDim, args.npl, v);
     }
   }
+}
+
+__global__ __launch_bounds__(256) void transpose_in_kernel(TransArgs args, int batch) {
+  transpose_in_body<false>(args, batch);
+}
+__global__ __launch_bounds__(256) void transpose_in_counts_kernel(TransArgs args, int batch) {
+  transpose_in_body<true>(args, batch);
 }
 
 // Linear-attention source state.  The qkv GEMM's epilogue (EPI_QKV) leaves, per 32-token
@@ -950,14 +966,18 @@ __device__ __forceinline__ unsigned long long shfl_xor_u64(unsigned long long v,
 constexpr int kConfColTiles = 16;   // column partials (score M-tiles) the fused form takes
 constexpr int kConfRowTiles = 64;   // row partials (score N-tiles) the fused form takes
 constexpr int kConfWaves = 8, kConfRows = 4;   // 32 rows per workgroup: 8 waves x 4 rows
-template <bool VEC, bool STATS>
+// CNT (onepose_match_cached_counts): rows at or past the sample's count (counts[b], clamped to
+// [0, n1]) are written as zeros (with write_conf) and name no winner -- neither their own nor a
+// column's; the column statistics come from the counts score epilogue (rows below the count).
+template <bool VEC, bool STATS, bool CNT = false>
 __global__ __launch_bounds__(kConfWaves * 64) void conf_kernel(float* S, int n1, int n3,
                                                    const float* rowmax, const float* rowsum,
                                                    const float* colmax, const float* colsum,
                                                    unsigned long long* rowpart,
                                                    unsigned long long* colbest, int write_conf,
                                                    int col_offset, const float* srow, int nt3,
-                                                   const float* scol, int mt1) {
+                                                   const float* scol, int mt1,
+                                                   const int* counts) {
   constexpr int RW = kConfRows;
   __shared__ unsigned long long cb[kConfWaves][256];
   __shared__ float cst[2][STATS ? 256 : 1];
@@ -966,6 +986,7 @@ __global__ __launch_bounds__(kConfWaves * 64) void conf_kernel(float* S, int n1,
   const int b = blockIdx.y;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   float* Sb = S + (int64_t)b * n1 * n3;
+  const int cn = CNT ? min(max(counts[b], 0), n1) : n1;
   float rst[STATS ? RW : 1][2];   // STATS: the wave's rows' (max, 1 / sum)
   // The workgroup's S block first: its loads do not depend on the statistics, so they are in
   // flight while the statistics' partials load and reduce (one round trip instead of three).
@@ -1077,6 +1098,19 @@ __global__ __launch_bounds__(kConfWaves * 64) void conf_kernel(float* S, int n1,
   for (int i = 0; i < RW; ++i) {
     const int n = tiler * 32 + wave * RW + i;
     if (n >= n1) break;   // wave-uniform
+    if (CNT && n >= cn) {   // a padded row: conf 0, no winner (rk[i] stays 0); wave-uniform
+      if (write_conf) {
+        float* ps = Sb + (int64_t)n * n3;
+        if (VEC && cok[0]) {
+          *reinterpret_cast<float4*>(ps + col[0]) = make_float4(0.f, 0.f, 0.f, 0.f);
+        } else {
+#pragma unroll
+          for (int j = 0; j < 4; ++j)
+            if (cok[j]) ps[col[j]] = 0.f;
+        }
+      }
+      continue;
+    }
     float rmx, rinv;
     if constexpr (STATS) {
       rmx = rst[i][0];
@@ -1184,9 +1218,26 @@ __global__ __launch_bounds__(256) void mutual_kernel(const unsigned long long* r
                                                      const unsigned long long* colbest,
                                                      int batch, int n1, int n3, float thr,
                                                      int64_t* matches0, int64_t* matches1,
-                                                     float* ms0, float* ms1, const unsigned* err) {
+                                                     float* ms0, float* ms1, const unsigned* err,
+                                                     const int* counts) {
   const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
   const int64_t nr = (int64_t)batch * n1, nc = (int64_t)batch * n3;
+  if (counts != nullptr && idx < nr + nc) {
+    // per-sample row counts (onepose_match_cached_counts): rows past the count, and every row and
+    // column of an empty sample, have no match (conf_kernel<., ., true> named no winner there)
+    const int b = idx < nr ? (int)(idx / n1) : (int)((idx - nr) / n3);
+    const int cn = min(max(counts[b], 0), n1);
+    if (idx < nr && (int)(idx - (int64_t)b * n1) >= cn) {
+      ms0[idx] = 0.f;
+      matches0[idx] = -1;
+      return;
+    }
+    if (idx >= nr && cn == 0) {
+      ms1[idx - nr] = 0.f;
+      matches1[idx - nr] = -1;
+      return;
+    }
+  }
   if (err != nullptr && *err != 0u) {   // the forward read a stale object cache: no match
     if (idx < nr) {
       ms0[idx] = 0.f;
@@ -1319,6 +1370,14 @@ int qkv_tile_for(int n3, int B) {
 static_assert(gemm_has_variant(EPI_QKV, PRO_PLAIN, TILE_128x128, PM_F32, false, 0) &&
                   gemm_has_variant(EPI_QKV, PRO_PLAIN, TILE_128x128W8, PM_F32, false, 0),
               "qkv_tile_for's wide tiles");
+
+// the counts entry points' kernels (fp32 only): the 2D side's QKV on any of qkv_tile_for's tiles
+static_assert(gemm_has_variant(EPI_QKV_CNT, PRO_PLAIN, kTileKV, PM_F32, false, 0) &&
+                  gemm_has_variant(EPI_QKV_CNT, PRO_PLAIN, TILE_128x128W8, PM_F32, false, 0) &&
+                  gemm_has_variant(EPI_QKV_CNT, PRO_PLAIN, TILE_128x128, PM_F32, false, 0) &&
+                  gemm_has_variant(EPI_STATS_CNT, PRO_HEADZ, kTileMLP1, PM_F32, false, 0) &&
+                  gemm_has_variant(EPI_SCORE_CNT, PRO_PLAIN, kTileScore, PM_F32, false, 0),
+              "fp32 tiles with per-sample counts");
 
 bool valid_precision(int p) {
   return p == ONEPOSE_PREC_FP32 || p == ONEPOSE_PREC_BF16_ATTN || p == ONEPOSE_PREC_FP32_SPLIT;
@@ -1507,6 +1566,9 @@ struct Side {
   int64_t xp_bs = 0;
   uint16_t* xop = nullptr;
   uint16_t* phiqp = nullptr;
+  // [B] int32 device counts of the side's real tokens, or null: every token (the 3D side, and
+  // every side of a call without counts).  n stays the padded length.
+  const int* counts = nullptr;
 };
 
 // Choices of one attention layer that change a side's summation order: the QKV tile of the
@@ -1660,6 +1722,7 @@ int attention_layer(const ApW& w, const Side* sd, int nside, int B, const Plan& 
       g = gemm_prob(s.x, 256, w.wqkv, 256, w.bqkv, s.phiq, 256, s.n, 768, 256, B);
       g.a0_bs = s.x_bs;
       g.vdiv = s.len;
+      g.counts = s.counts;
       g.kvpart = s.kvpart;
       g.kspart = s.kspart;
       g.y_bs = (int64_t)s.n * 256;
@@ -1760,6 +1823,8 @@ int attention_layer(const ApW& w, const Side* sd, int nside, int B, const Plan& 
       a.p[i].ksum = p.ksum + (size_t)s.src * B * 256;
       a.p[i].ksum_bs = 256;
       a.p[i].ns = sd[s.src].len;
+      a.p[i].counts = s.counts;
+      a.p[i].ns_counts = sd[s.src].counts;
     }
     if (xc) {   // the object's halves: shared by the batch (batch stride 0)
       a.p[0].W1 = xc->mf;
@@ -1876,6 +1941,8 @@ struct MatchCall {
   CacheHdr obj_hdr{};
   // the stages [first_stage, last_stage] of the forward (onepose_match_cached_stages)
   int first_stage = ONEPOSE_STAGE_INPUTS, last_stage = ONEPOSE_STAGE_WINNERS;
+  // onepose_match_cached_counts: [batch] int32 device counts of the 2D side, or null
+  const int* counts2d = nullptr;
 };
 
 // What onepose_object_prepare built into each cache, keyed by the cache's device address. The
@@ -1967,8 +2034,11 @@ TransArgs transpose_args(const TransProb& a, const TransProb& b, unsigned* zero,
   return TransArgs{{a, b}, zero, nzero};
 }
 int launch_transpose(const TransArgs& ta, int B, hipStream_t st) {
-  OP_LAUNCH(K_TRANSPOSE, st, transpose_in_kernel, dim3((ta.p[0].tiles + ta.p[1].tiles) * B),
-            dim3(256), 0, st, ta, B);
+  const dim3 grid((ta.p[0].tiles + ta.p[1].tiles) * B);
+  if (ta.p[0].counts != nullptr || ta.p[1].counts != nullptr)
+    OP_LAUNCH(K_TRANSPOSE, st, transpose_in_counts_kernel, grid, dim3(256), 0, st, ta, B);
+  else
+    OP_LAUNCH(K_TRANSPOSE, st, transpose_in_kernel, grid, dim3(256), 0, st, ta, B);
   return ONEPOSE_OK;
 }
 
@@ -2048,6 +2118,7 @@ int stage_inputs(Forward& f) {
       trans_prob(c.desc3d, c.desc3d_bs, c.n3, !cached && f16, !cached, p.x3[0], f.pl(p.x3p[0])),
       p.cnt, p.ncnt);
   ta.npl = f.npl;
+  ta.p[0].counts = c.counts2d;
   if (f.conf_stats) {
     ta.zero64 = p.colbest;
     ta.nzero64 = (int64_t)c.batch * c.n3;
@@ -2102,11 +2173,12 @@ int attention_stage(Forward& f, int layer, bool run) {
   const int a = f.ap++;
   const ApW w = ap_weights(f.wbase, a);
   const int ntile3 = sh ? sh->max_shard : n3;
-  const Side sd[2] = {
+  Side sd[2] = {
       make_side(p, 0, f.npl, f.x2r, (int64_t)n1 * 256, f.x2pr, p.x2[c2 ^ 1], p.x2p[c2 ^ 1], n1,
                 (float)n1, cross ? 1 : 0, n1),
       make_side(p, 1, f.npl, f.x3r, f.x3bs, f.x3pr, p.x3[c3 ^ 1], p.x3p[c3 ^ 1], n3,
                 (float)f.n3g, cross ? 0 : 1, ntile3)};
+  sd[0].counts = c.counts2d;
   unsigned* lcnt = p.cnt + (size_t)a * 2 * B * p.cps;
   // layers 1-2 of a whole frame: per-side choices (the 3D side's are the object prefix's,
   // so cached and uncached forwards agree bit for bit at any batch); later layers and
@@ -2179,6 +2251,7 @@ int stage_score(Forward& f) {
   a.p[0].scale = c.scale_factor;
   a.p[0].rowstat = p.rowpart;
   a.p[0].colstat = p.colpart;
+  a.p[0].counts = c.counts2d;   // (column partials over each sample's own rows)
   return gemm_launch(EPI_SCORE, PRO_PLAIN, score_tile, a, c.stream, K_SCORE, f.pm_out);
 }
 
@@ -2210,17 +2283,25 @@ int stage_winners(Forward& f) {
   }
   const int coff = sh ? sh->offset : 0;
   const dim3 cgrid(ceil_div(n1, 32) * ceil_div(n3, 256), B);
-#define CONF_LAUNCH(V, ST)                                                                   \
-  OP_LAUNCH(K_CONF, st, (conf_kernel<V, ST>), cgrid, dim3(kConfWaves * 64), 0, st, S, n1, n3,  \
-            p.rowmax,                                                                       \
+#define CONF_LAUNCH(V, ST, CN)                                                               \
+  OP_LAUNCH(K_CONF, st, (conf_kernel<V, ST, CN>), cgrid, dim3(kConfWaves * 64), 0, st, S, n1,  \
+            n3, p.rowmax,                                                                   \
             p.rowsum, p.colmax, p.colsum, p.rowwin, p.colbest, with_conf ? 1 : 0, coff,     \
-            p.rowpart, ch3, p.colpart, score_mt)
-  if (n3 % 4 == 0) {
-    if (f.conf_stats) CONF_LAUNCH(true, true);
-    else CONF_LAUNCH(true, false);
+            p.rowpart, ch3, p.colpart, score_mt, c.counts2d)
+  if (c.counts2d == nullptr) {
+    if (n3 % 4 == 0) {
+      if (f.conf_stats) CONF_LAUNCH(true, true, false);
+      else CONF_LAUNCH(true, false, false);
+    } else {
+      if (f.conf_stats) CONF_LAUNCH(false, true, false);
+      else CONF_LAUNCH(false, false, false);
+    }
+  } else if (n3 % 4 == 0) {
+    if (f.conf_stats) CONF_LAUNCH(true, true, true);
+    else CONF_LAUNCH(true, false, true);
   } else {
-    if (f.conf_stats) CONF_LAUNCH(false, true);
-    else CONF_LAUNCH(false, false);
+    if (f.conf_stats) CONF_LAUNCH(false, true, true);
+    else CONF_LAUNCH(false, false, true);
   }
 #undef CONF_LAUNCH
   const unsigned long long* colbest = p.colbest;
@@ -2248,7 +2329,7 @@ int stage_winners(Forward& f) {
   const int64_t tot_g = (int64_t)B * (n1 + n3g);
   OP_LAUNCH(K_MUTUAL, st, mutual_kernel, dim3((unsigned)((tot_g + 255) / 256)), dim3(256), 0, st,
             p.rowbest, rowwin, ceil_div(n3, 256), colbest, B, n1, n3g, c.match_threshold,
-            c.matches0, c.matches1, c.mscores0, c.mscores1, p.err);
+            c.matches0, c.matches1, c.mscores0, c.mscores1, p.err, c.counts2d);
   return ONEPOSE_OK;
 }
 
@@ -2374,6 +2455,17 @@ int object_prepare_impl(const void* packed_weights, const void* desc3d, int desc
 }  // namespace onepose
 
 extern "C" {
+
+static int match_cached_stages_impl(bool with_counts, const void* packed_weights,
+                                    const void* desc2d, int desc_dtype, int64_t desc2d_bstride,
+                                    const float* object_cache, const float* leaves_prepared,
+                                    int64_t prepared_bstride, int batch, int n1, int n3,
+                                    int num_leaf, float scale_factor, float match_threshold,
+                                    int precision, int object_flags, const int* counts2d,
+                                    int64_t* matches0, int64_t* matches1, float* mscores0,
+                                    float* mscores1, float* conf, void* workspace,
+                                    size_t workspace_bytes, int first_stage, int last_stage,
+                                    void* stream_);
 
 size_t onepose_leaves_prepared_bytes(int batch, int n3, int num_leaf) {
   if (batch <= 0 || n3 <= 0 || num_leaf <= 0) return 0;
@@ -2607,6 +2699,26 @@ int onepose_match_cached_stages(const void* packed_weights, const void* desc2d, 
                                float* mscores1, float* conf, void* workspace,
                                size_t workspace_bytes, int first_stage, int last_stage,
                                void* stream_) {
+  return match_cached_stages_impl(false, packed_weights, desc2d, desc_dtype, desc2d_bstride,
+                                  object_cache, leaves_prepared, prepared_bstride, batch, n1, n3,
+                                  num_leaf, scale_factor, match_threshold, precision,
+                                  object_flags, nullptr, matches0, matches1, mscores0, mscores1,
+                                  conf, workspace, workspace_bytes, first_stage, last_stage,
+                                  stream_);
+}
+
+// onepose_match_cached_stages, and the counts family's entry (with_counts: fp32 only, counts2d a
+// [batch] int32 device array or null)
+static int match_cached_stages_impl(bool with_counts, const void* packed_weights,
+                                    const void* desc2d, int desc_dtype, int64_t desc2d_bstride,
+                                    const float* object_cache, const float* leaves_prepared,
+                                    int64_t prepared_bstride, int batch, int n1, int n3,
+                                    int num_leaf, float scale_factor, float match_threshold,
+                                    int precision, int object_flags, const int* counts2d,
+                                    int64_t* matches0, int64_t* matches1, float* mscores0,
+                                    float* mscores1, float* conf, void* workspace,
+                                    size_t workspace_bytes, int first_stage, int last_stage,
+                                    void* stream_) {
   clear_error();
   OP_REQUIRE(first_stage >= ONEPOSE_STAGE_INPUTS && first_stage <= last_stage &&
                  last_stage <= ONEPOSE_STAGE_WINNERS,
@@ -2615,6 +2727,11 @@ int onepose_match_cached_stages(const void* packed_weights, const void* desc2d, 
              "match_cached: dtype %d", desc_dtype);
   OP_REQUIRE(valid_precision(precision),
              "match_cached: precision %d", precision);
+  if (with_counts && precision != ONEPOSE_PREC_FP32) {
+    set_error("match_cached_counts: precision %d: per-sample counts are ONEPOSE_PREC_FP32 only",
+              precision);
+    return ONEPOSE_ERR_UNSUPPORTED;
+  }
   OP_REQUIRE((object_flags & ~ONEPOSE_OBJ_GAT_TABLES) == 0, "match_cached: flags %d",
              object_flags);
   MatchCall c;
@@ -2628,9 +2745,50 @@ int onepose_match_cached_stages(const void* packed_weights, const void* desc2d, 
   c.matches0 = matches0; c.matches1 = matches1; c.mscores0 = mscores0; c.mscores1 = mscores1;
   c.conf = conf;
   c.first_stage = first_stage; c.last_stage = last_stage;
+  c.counts2d = counts2d;
   Plan p;
   const int rc = checked_plan("match_cached", &c, leaves_prepared, workspace, workspace_bytes, &p);
   return rc != ONEPOSE_OK ? rc : match_impl(c, p);
+}
+
+int onepose_match_counts_version(void) { return 1; }
+
+size_t onepose_match_counts_workspace_bytes(int batch, int n1, int n3, int num_leaf, int with_conf,
+                                            int precision) {
+  return onepose_match_workspace_bytes_ex(batch, n1, n3, num_leaf, with_conf, precision);
+}
+
+int onepose_match_cached_counts_stages(const void* packed_weights, const void* desc2d,
+                                       int desc_dtype, int64_t desc2d_bstride,
+                                       const float* object_cache, const float* leaves_prepared,
+                                       int64_t prepared_bstride, int batch, int n1, int n3,
+                                       int num_leaf, float scale_factor, float match_threshold,
+                                       int precision, int object_flags, const int* counts2d,
+                                       int64_t* matches0, int64_t* matches1, float* mscores0,
+                                       float* mscores1, float* conf, void* workspace,
+                                       size_t workspace_bytes, int first_stage, int last_stage,
+                                       void* stream_) {
+  return match_cached_stages_impl(true, packed_weights, desc2d, desc_dtype, desc2d_bstride,
+                                  object_cache, leaves_prepared, prepared_bstride, batch, n1, n3,
+                                  num_leaf, scale_factor, match_threshold, precision,
+                                  object_flags, counts2d, matches0, matches1, mscores0, mscores1,
+                                  conf, workspace, workspace_bytes, first_stage, last_stage,
+                                  stream_);
+}
+
+int onepose_match_cached_counts(const void* packed_weights, const void* desc2d, int desc_dtype,
+                                int64_t desc2d_bstride, const float* object_cache,
+                                const float* leaves_prepared, int64_t prepared_bstride, int batch,
+                                int n1, int n3, int num_leaf, float scale_factor,
+                                float match_threshold, int precision, int object_flags,
+                                const int* counts2d, int64_t* matches0, int64_t* matches1,
+                                float* mscores0, float* mscores1, float* conf, void* workspace,
+                                size_t workspace_bytes, void* stream_) {
+  return onepose_match_cached_counts_stages(
+      packed_weights, desc2d, desc_dtype, desc2d_bstride, object_cache, leaves_prepared,
+      prepared_bstride, batch, n1, n3, num_leaf, scale_factor, match_threshold, precision,
+      object_flags, counts2d, matches0, matches1, mscores0, mscores1, conf, workspace,
+      workspace_bytes, ONEPOSE_STAGE_INPUTS, ONEPOSE_STAGE_WINNERS, stream_);
 }
 
 int onepose_match_workspace_region(int batch, int n1, int n3, int num_leaf, int with_conf,

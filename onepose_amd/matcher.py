@@ -14,6 +14,13 @@ the same ``forward(data) -> (pred, conf_matrix)`` contract as
   ``skip_train`` (:223-231);
 * a ``match_type`` other than ``'softmax'`` raises ``NotImplementedError`` (:275-276).
 
+onepose_amd extension: the optional key ``keypoints2d_counts`` ([B] int32 / int64 on the inputs'
+device) gives each sample's number of real 2D keypoints in a batch padded to N1
+(``onepose_match_cached_counts``, include/onepose_match_counts.h; fp32 attention, one object for
+the whole batch: 3D tensors of batch 1 or expanded).  Sample b is matched as if it had that many
+keypoints; ``pred`` stays batch element 0 at the padded length (-1 / 0 past its count) and
+``conf_matrix`` [B, N1, N3] has zero rows past each count.  Without the key nothing changes.
+
 The parameters are ordinary ``nn.Parameter``s (PyTorch is the weight store); the first
 forward after they change packs them (head-major q/k/v, folded GAT vectors) into one
 device-resident panel.  The module has no CPU path: tensors must live on a ROCm device
@@ -201,6 +208,7 @@ class GATsSuperGlue(nn.Module):
         d2, s2 = self._operand(data["descriptors2d_query"], half)
         d3, s3 = self._operand(data["descriptors3d_db"], half)
         db, sl = self._operand(data["descriptors2d_db"], half)
+        cnt = self._counts_arg(data.get("keypoints2d_counts"), d2, data)
         if d2.device.type != "cuda":
             raise RuntimeError("onepose_amd.GATsSuperGlue runs on a ROCm GPU only; "
                                "move the inputs with .cuda()")
@@ -211,6 +219,8 @@ class GATsSuperGlue(nn.Module):
             raise ValueError(f"bad matcher input shapes {tuple(d2.shape)} {tuple(d3.shape)} "
                              f"{tuple(db.shape)}")
         dev = d2.device
+        if cnt is not None:
+            return self._forward_counts(data, cnt, d2, s2, d3, db, B, n1, n3, nleaf, half, dev)
         obj = None
         # (inference tensors carry no version counter, so an in-place write to the object could
         # not be detected: they take the uncached forward, the same bits)
@@ -221,6 +231,39 @@ class GATsSuperGlue(nn.Module):
             obj = self._resident(data["descriptors3d_db"], data["descriptors2d_db"], d3, db, n3,
                                  nleaf, half, dev)
         return self._run(d2, s2, d3, s3, db, sl, B, n1, n3, nleaf, dev, obj)
+
+    def _counts_arg(self, cnt, d2, data):
+        """``keypoints2d_counts`` checked (before anything touches the device): None, or a [B]
+        int32 / int64 tensor on the descriptors' device, for fp32 attention and one object."""
+        if cnt is None:
+            return None
+        if not torch.is_tensor(cnt) or cnt.dtype not in (torch.int32, torch.int64):
+            raise TypeError("keypoints2d_counts must be an int32 or int64 tensor, not "
+                            f"{cnt.dtype if torch.is_tensor(cnt) else type(cnt).__name__}")
+        if tuple(cnt.shape) != (d2.shape[0],):
+            raise ValueError(f"keypoints2d_counts of shape {tuple(cnt.shape)}: expected "
+                             f"({d2.shape[0]},), one count per sample")
+        if cnt.device != d2.device:
+            raise ValueError(f"keypoints2d_counts on {cnt.device}, descriptors on {d2.device}")
+        if self.precision != PRECISIONS["fp32"]:
+            raise ValueError("keypoints2d_counts: attention_precision 'fp32' only")
+        for k in ("descriptors3d_db", "descriptors2d_db"):
+            if data[k].shape[0] != 1 and data[k].stride(0) != 0:
+                raise ValueError(f"keypoints2d_counts: {k} must be one object for the batch "
+                                 "(batch 1, or expanded along the batch)")
+        return cnt.to(torch.int32).contiguous()
+
+    def _forward_counts(self, data, cnt, d2, s2, d3, db, B, n1, n3, nleaf, half, dev):
+        t3, tl = data["descriptors3d_db"], data["descriptors2d_db"]
+        if torch.is_inference(t3) or torch.is_inference(tl):   # untracked: prepared per call
+            with torch.cuda.device(dev):
+                obj = PreparedObject(self.packed_weights(dev), d3[:1], db[:1], self.precision)
+            try:
+                return self._run(d2, s2, None, 0, None, 0, B, n1, n3, nleaf, dev, obj, cnt)
+            finally:
+                obj.release()
+        obj = self._resident(t3, tl, d3[:1], db[:1], n3, nleaf, half, dev)
+        return self._run(d2, s2, None, 0, None, 0, B, n1, n3, nleaf, dev, obj, cnt)
 
     # The reference's driver calls forward() once per frame with the same object tensors
     # (inference.py:98-182: load_object once, pack_data per frame).  With resident_object, the
@@ -252,7 +295,7 @@ class GATsSuperGlue(nn.Module):
         if cur is not None:
             cur["prepared"].release()
 
-    def _run(self, d2, s2, d3, s3, db, sl, B, n1, n3, nleaf, dev, obj=None):
+    def _run(self, d2, s2, d3, s3, db, sl, B, n1, n3, nleaf, dev, obj=None, counts=None):
         lib = _lib.load()
         with torch.cuda.device(dev):
             w = self.packed_weights(dev)
@@ -273,6 +316,11 @@ class GATsSuperGlue(nn.Module):
             if obj is not None:
                 # built on another stream: this forward runs behind the prepare
                 obj.use_on(torch.cuda.current_stream(dev))
+            if counts is not None:
+                _lib.run("onepose_match_cached_counts", desc_dtype=dt, object_cache=obj.cache,
+                         leaves_prepared=obj.leaves_pm, prepared_bstride=0, object_flags=0,
+                         counts2d=counts, **args)
+            elif obj is not None:
                 _lib.run("onepose_match_cached_dt", desc_dtype=dt, object_cache=obj.cache,
                          leaves_prepared=obj.leaves_pm, prepared_bstride=0, object_flags=0, **args)
             else:

@@ -30,10 +30,15 @@ transpose [-> self-attention 1]) of the frame that next uses the slot
 With a ``detector`` (``onepose_amd.superpoint.SuperPoint``) the pipeline starts from images
 (``extract_features.py`` + ``inference.py:143``): each slot owns an image buffer and the
 detector writes its keypoints / descriptors straight into that slot's matcher inputs
-([B, n1, 2] and [B, 256, n1], n1 = max_keypoints).  The matcher then runs at n1 keypoints, so
-the graph-replayed path is exact when the detector fills its top-k (``det_counts`` == n1, the
-512x512 crops' usual case); frames with fewer keypoints belong on ``inference.run_frames``,
-which runs each frame at its own size.
+([B, n1, 2] and [B, 256, n1], n1 = max_keypoints).  The matcher's launches are sized for n1
+keypoints.  With ``variable_counts=True`` each slot's matcher stages also receive that slot's
+``det_counts`` (``onepose_match_cached_counts_stages``, include/onepose_match_counts.h): a frame
+on which the detector found c < n1 keypoints is matched as if its 2D side had c tokens, entirely
+on the device, so the graph-replayed path equals ``inference.run_frames`` -- which runs each frame
+at its own size -- on partly filled frames too (rows past c: no match).  The staged schedule is
+kept: a slot's next input stage runs behind its detector on the same stream, so the counts are
+there when it reads them.  Without it (the default) the pipeline issues the uniform calls,
+which are exact when the detector fills its top-k (``det_counts`` == n1).
 """
 from __future__ import annotations
 
@@ -93,8 +98,11 @@ class FramePipeline:
                  device, scale: float = 1000.0, reprojection_error: float = 5.0,
                  iterations_count: int = 10000, confidence: float = 0.99, with_conf=False,
                  slots: int = 2, detector=None, image_hw=(512, 512), object_cache: bool = True,
-                 gat_tables: bool = True, desc_dtype: str = "fp32"):
-        """desc_dtype "fp16": the object's descriptors / leaves and the query descriptors are held
+                 gat_tables: bool = True, desc_dtype: str = "fp32",
+                 variable_counts: bool = False):
+        """variable_counts: with a detector, match each frame at its own keypoint count (the
+        slot's ``det_counts``, read on the device; fp32 attention and the object cache only).
+        desc_dtype "fp16": the object's descriptors / leaves and the query descriptors are held
         in fp16 on the device (BASELINE config 5's "fp16 desc"); the kernels convert them as they
         load them, which is the reference's .float() upcast (GATs_SuperGlue.py:219-221), so the
         results are those of the fp32 pipeline on the fp16-rounded inputs, bit for bit."""
@@ -143,6 +151,13 @@ class FramePipeline:
         self.K = torch.zeros(B, 3, 3, dtype=torch.float64, device=dev)
         self.pose_gt = torch.zeros(B, 3, 4, dtype=torch.float64, device=dev)
         self.detector = detector
+        self.variable_counts = bool(variable_counts)
+        if self.variable_counts:
+            if detector is None or not object_cache:
+                raise ValueError("variable_counts: the counts are the detector's, and the counts "
+                                 "entry points are the object-cached ones")
+            if self.precision != 0:
+                raise ValueError("variable_counts: attention_precision 'fp32' only")
         if detector is not None:
             cap = detector.capacity(*image_hw)
             if cap != n1:
@@ -258,7 +273,11 @@ class FramePipeline:
                     matches0=o.matches0, matches1=o.matches1, mscores0=o.mscores0,
                     mscores1=o.mscores1, conf=o._conf, workspace=o.ws_match,
                     workspace_bytes=o.ws_match_bytes, stream=s)
-        if self.object_cache is not None:
+        if self.variable_counts:
+            _lib.run("onepose_match_cached_counts_stages", desc_dtype=self.desc_dt,
+                     object_cache=self.object_cache, object_flags=self.object_flags,
+                     counts2d=o.det_counts, first_stage=stages[0], last_stage=stages[1], **args)
+        elif self.object_cache is not None:
             _lib.run("onepose_match_cached_stages", desc_dtype=self.desc_dt,
                      object_cache=self.object_cache, object_flags=self.object_flags,
                      first_stage=stages[0], last_stage=stages[1], **args)
